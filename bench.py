@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """Contract benchmark: videos/sec of the GVL (PDVC) eval forward AND train-step ms on N MI355X GPUs, in one JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode both|eval|train] [--T 100] [--queries 300]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--mode both|eval|train] [--T 100]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed eval steps, and the line with
+`metric`, `value` (eval videos/s), `unit`, `higher_is_better`, `dtype` and `ms_per_step`.  `--full` adds everything else
+described below: the train half (default `--mode both` instead of `eval`), the kernel stamps and roofline blocks, the A/Bs
+of the same step on other GEMM / layer paths and under autocast, the kernel / GEMM probes, the in-graph kernel trace, the
+shader clock and the CPU baseline.  `--dump-outputs DIR` writes what the timed path returned in its last timed step (every
+tensor of the eval forward's result and losses, and of the train step's when the train half runs) as DIR/<name>.npy in
+float32 / float64; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 A *step* is one pass of the hot path over one batch of synthetic input: ``PDVC.forward(dt, criterion, None,
 'queries', eval_mode=True)`` (eval_utils.py:203) -- or, for the second half of BASELINE.json's metric, one training
@@ -41,6 +49,49 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_TBS = 8.0           # MI355X HBM3E peak (MI355X_MICROARCH.md)
 PMC_FILE = os.path.join("profiles", "r06_pmc_traffic.json")
+DUMP_CAP_BYTES = 60 * 2 ** 20      # --dump-outputs: array bytes in all (the files, headers included, stay under 64 MB)
+
+
+# loss terms left out of --dump-outputs: the self-IoU of the matched predictions (criterion.py:123-130 of the reference) is a mean
+# over the pairs of a video -- 0/0 = NaN for every video with fewer than two matched events, which the rotating batches always
+# hold -- and carries no weight in the loss; the tests leave it out of their finiteness checks for the same reason
+DUMP_SKIP_KEYS = ("loss_self_iou",)
+
+
+def host_arrays(obj, name, acc):
+    """the tensors of a step's result (nested dicts / lists / tuples; the matcher's device-resident LayerMatch as its query
+    and target ids) as host arrays keyed by their path: float64 stays float64, integers and booleans become float64
+    (exact), every other floating type float32.  Dict entries named DUMP_SKIP_KEYS (or with a layer suffix) are left out."""
+    from gvl_amd.matcher import LayerMatch
+    if isinstance(obj, torch.Tensor):
+        t = obj.detach().cpu()
+        acc[name] = (t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()).numpy()
+    elif isinstance(obj, LayerMatch):
+        host_arrays({"q": obj.q, "t": obj.t}, name, acc)
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            if not str(k).startswith(DUMP_SKIP_KEYS):
+                host_arrays(v, f"{name}.{k}", acc)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            host_arrays(v, f"{name}.{i}", acc)
+    return acc
+
+
+def write_outputs(arrays, out_dir, cap=DUMP_CAP_BYTES):
+    """DIR/<name>.npy per array; when the whole set exceeds `cap`, every array larger than an equal share of it is
+    replaced by a fixed seeded sample of its flattened elements (ascending positions), written as <name>.sample.npy"""
+    import re
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    over = sum(a.nbytes for a in arrays.values()) > cap
+    for name, arr in arrays.items():
+        fname = re.sub(r"[^A-Za-z0-9_.-]", "_", name)
+        share = max(1, cap // max(1, len(arrays)) // arr.itemsize)
+        if over and arr.size > share:
+            idx = np.sort(np.random.RandomState(0).choice(arr.size, share, replace=False))
+            arr, fname = arr.reshape(-1)[idx], fname + ".sample"
+        np.save(os.path.join(out_dir, fname + ".npy"), arr)
 
 
 def synth_batch(B, T, feat, vocab, n_gt, device, seed=1, cap_words=10):
@@ -93,7 +144,7 @@ def in_graph_kernel_us(a, mode):
         return {"error": "rocprofv3 not found"}
     out = tempfile.mkdtemp(prefix="gvl_ingraph_", dir="/tmp")
     cmd = [exe, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "bench.py"),
-           "--mode", mode, "--no-cpu-baseline", "--no-probes", "--steps", "20", "--warmup", "5", "--batch", str(a.batch),
+           "--mode", mode, "--full", "--no-cpu-baseline", "--no-probes", "--steps", "20", "--warmup", "5", "--batch", str(a.batch),
            "--T", str(a.T), "--queries", str(a.queries), "--cfg", a.cfg, "--rotate", str(a.rotate)]
     try:
         env = dict(os.environ, TMPDIR="/tmp")
@@ -339,9 +390,9 @@ def cpu_baseline(model, opt, T, budget_s=30.0):
                                      f"(runs {', '.join(f'{x:.2f}' for x in tt)} s)"}}
 
 
-def timed_loop(step, batches, steps, warmup, world, dev):
+def timed_loop(step, batches, steps, warmup, world, dev, clock=True):
     """W untimed warm-up steps, then EXACTLY K timed steps between barrier + synchronize; -> elapsed seconds (max over
-    ranks), per-rank seconds"""
+    ranks), per-rank seconds.  clock: probe the shader clock right behind the steps (timed_loop.last_clock_mhz)"""
     for i in range(warmup):
         o_ = step(batches[i % len(batches)])
         if os.environ.get("GVL_BENCH_TRACE_LOSS") and isinstance(o_, tuple) and isinstance(o_[0], torch.Tensor) and o_[0].numel() == 1:
@@ -387,9 +438,11 @@ def timed_loop(step, batches, steps, warmup, world, dev):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    timed_loop.last_clock_mhz = None
     try:                                   # the shader clock right behind the timed steps (diagnostic; outside the timing)
-        from gvl_amd import MultiScaleDeformableAttention as _M
-        timed_loop.last_clock_mhz = round(_M.clock_probe_mhz(dev, 4000), 0)
+        if clock:
+            from gvl_amd import MultiScaleDeformableAttention as _M
+            timed_loop.last_clock_mhz = round(_M.clock_probe_mhz(dev, 4000), 0)
     except Exception:                      # noqa: BLE001
         timed_loop.last_clock_mhz = None
     per_rank = [elapsed]
@@ -458,7 +511,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--mode", default="both", choices=["both", "eval", "train"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline eval figure: the train half, kernel stamps / rooflines, A/Bs, probes, "
+                         "in-graph kernel trace, shader clock and CPU baseline (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--mode", default=None, choices=["both", "eval", "train"],
+                    help="default: eval, or both with --full")
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--queries", type=int, default=300)
     ap.add_argument("--batch", type=int, default=16, help="videos per GPU")
@@ -485,6 +544,10 @@ def main():
     ap.add_argument("--launch-timeout", type=float, default=3000.0,
                     help="seconds the self-launched ranks of `python bench.py --gpus N` (N > 1, no launcher) may take")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.mode is None:
+        a.mode = "both" if a.full else "eval"
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # `python bench.py --gpus N` without a launcher: this process has not touched the GPU (no HIP call so far, and
@@ -540,6 +603,7 @@ def main():
     from gvl_amd.pdvc import autocast_inference_policy as _aip
     vb_eval = 4 if (a.dtype == "f32" or _aip() != "bf16") else 2      # (autocast inference on the fp32-storage kernels)
     res = {}
+    dumped = {}                         # --dump-outputs: name -> host array of the last timed step(s)
 
     def traffic_of(cfg_key, launch):
         """HBM bytes per launch from the committed rocprofv3 --pmc passes (tools/pmc_run.sh: FETCH_SIZE and WRITE_SIZE in
@@ -585,16 +649,21 @@ def main():
             step(dt)                # fits, library handles, lazily built constants)
         caps0 = graphed_eval.captures if graphed_eval else 0
         MSDA.profile_enable(a.no_graph)
-        elapsed, per_rank = timed_loop(step, batches, a.steps, a.warmup, world, dev)
+        elapsed, per_rank = timed_loop(step, batches, a.steps, a.warmup, world, dev, clock=a.full)
+        if a.dump_outputs and rank == 0:
+            dumped.update(host_arrays(timed_loop.last_out, "eval", {}))
         eval_clock = getattr(timed_loop, "last_clock_mhz", None)
         MSDA.profile_enable(False)
-        ktimes = kernel_times(MSDA.profile_collect()) if a.no_graph else instrumented(eager_eval)
-        # the hand-written projection GEMM in front of every sampling launch: stamped in a pass of its own (level 2)
-        MSDA.profile_enable(2)
-        eager_eval(batches[0])
-        torch.cuda.synchronize()
-        MSDA.profile_enable(False)
-        ktimes.update({k: v for k, v in kernel_times(MSDA.profile_collect()).items() if k[0] == "proj"})
+        ktimes = kernel_times(MSDA.profile_collect()) if a.no_graph else {}
+        if a.full:
+            if not a.no_graph:
+                ktimes = instrumented(eager_eval)
+            # the hand-written projection GEMM in front of every sampling launch: stamped in a pass of its own (level 2)
+            MSDA.profile_enable(2)
+            eager_eval(batches[0])
+            torch.cuda.synchronize()
+            MSDA.profile_enable(False)
+            ktimes.update({k: v for k, v in kernel_times(MSDA.profile_collect()).items() if k[0] == "proj"})
         res["eval"] = {"elapsed": elapsed, "per_rank": per_rank, "ktimes": ktimes, "clock_mhz": eval_clock,
                        "graphs": None if graphed_eval is None else {
                            "cached": len(graphed_eval.graphs), "captures_total": graphed_eval.captures,
@@ -610,7 +679,7 @@ def main():
         # gvl_gemm_f16x3 (fp32 operands split into fp16 (hi, residual) pairs that keep 22 significant bits, fp16 MFMA, fp32 accumulation): reported beside
         # `value`, never as `value`
         from gvl_amd.linear import split_gemm_enabled
-        if (split_gemm_enabled() and a.dtype == "f32" and not a.no_graph and not a.no_captioner and not a.no_probes):
+        if (a.full and split_gemm_enabled() and a.dtype == "f32" and not a.no_graph and not a.no_captioner and not a.no_probes):
             os.environ["GVL_GEMM"] = "f32"
             try:
                 g2 = GraphedEvalForward(model, criterion, autocast_dtype=ac, decode_chunk=a.decode_chunk)
@@ -626,7 +695,7 @@ def main():
         # A/B of the same step with the transformer layers / base encoder / heads in their PyTorch formulation (library
         # fp32 GEMMs, ATen elementwise) instead of the hand-written inference layers of gvl_amd/layers.py
         from gvl_amd import layers as _layers
-        if (_layers.enabled() and a.dtype == "f32" and not a.no_graph and not a.no_probes):
+        if (a.full and _layers.enabled() and a.dtype == "f32" and not a.no_graph and not a.no_probes):
             os.environ["GVL_LAYERS"] = "torch"
             try:
                 g3 = GraphedEvalForward(model, criterion, autocast_dtype=ac, decode_chunk=a.decode_chunk)
@@ -642,7 +711,7 @@ def main():
 
         # ... and with BOTH switches off: every Linear on the fp32 library GEMMs (exact fp32 products, no split-fp16 operands
         # anywhere) -- the number for a reader who does not accept 22-bit operands as fp32
-        if (_layers.enabled() and split_gemm_enabled() and a.dtype == "f32" and not a.no_graph and not a.no_captioner
+        if (a.full and _layers.enabled() and split_gemm_enabled() and a.dtype == "f32" and not a.no_graph and not a.no_captioner
                 and not a.no_probes):
             os.environ["GVL_LAYERS"] = "torch"
             os.environ["GVL_GEMM"] = "f32"
@@ -662,7 +731,7 @@ def main():
         # ... and the same step under torch.autocast(bfloat16) with the default autocast inference policy ("f16": the same
         # fp32-storage path with ONE fp16 product per fp32 product -- 11-bit operands where bf16 keeps 8; gvl_amd/pdvc.py):
         # a reduced-precision number, reported beside `value`, never as `value`
-        if (_layers.enabled() and split_gemm_enabled() and a.dtype == "f32" and not a.no_graph and not a.no_captioner
+        if (a.full and _layers.enabled() and split_gemm_enabled() and a.dtype == "f32" and not a.no_graph and not a.no_captioner
                 and not a.no_probes and _aip() == "f16"):
             g5 = GraphedEvalForward(model, criterion, autocast_dtype=torch.bfloat16, decode_chunk=a.decode_chunk)
             for dt in batches:
@@ -690,7 +759,9 @@ def main():
                 print(f"[trace] set-up call {i_}: loss {float(o_[0]):.4f}", file=sys.stderr, flush=True)
         caps0 = getattr(trainer, "captures", 0)
         MSDA.profile_enable(a.no_graph)
-        elapsed, per_rank = timed_loop(trainer, batches, a.steps, a.warmup, world, dev)
+        elapsed, per_rank = timed_loop(trainer, batches, a.steps, a.warmup, world, dev, clock=a.full)
+        if a.dump_outputs and rank == 0:
+            dumped.update(host_arrays(timed_loop.last_out, "train", {}))
         train_clock = [getattr(timed_loop, "last_clock_mhz", None)]
         last = getattr(timed_loop, "last_out", None)
         try:
@@ -700,9 +771,11 @@ def main():
         MSDA.profile_enable(False)
         if a.no_graph:
             ktimes = kernel_times(MSDA.profile_collect())
-        else:
+        elif a.full:
             ktimes = instrumented(lambda dt: TrainStep.__call__(trainer, dt))
             train_clock.append(round(MSDA.clock_probe_mhz(dev, 4000), 0))      # ... and behind the instrumented eager steps
+        else:
+            ktimes = {}
         xch = trainer.exchange_times_ms() if hasattr(trainer, "exchange_times_ms") else None
         res["train"] = {"elapsed": elapsed, "per_rank": per_rank, "ktimes": ktimes, "exchange_ms": xch, "clock_mhz": train_clock, "last_loss": last_loss,
                         "graphs": None if a.no_graph else {
@@ -835,8 +908,9 @@ def main():
         ms = e["elapsed"] * 1e3 / a.steps
         line.update({"metric": "videos/sec (eval fwd)", "value": round(world * B * a.steps / e["elapsed"], 3),
                      "unit": "videos/s", "ms_per_step": round(ms, 3), "higher_is_better": True,
-                     "roofline": fwd_roofline(e["ktimes"]), "eval_graphs": e["graphs"],
-                     "eval_seconds_per_rank": [round(x, 4) for x in e["per_rank"]]})
+                     "eval_graphs": e["graphs"], "eval_seconds_per_rank": [round(x, 4) for x in e["per_rank"]]})
+        if a.full:
+            line["roofline"] = fwd_roofline(e["ktimes"])
         kernels_us["eval"] = {ktag(k): {"us": round(v[0], 2), "n": v[1]} for k, v in e["ktimes"].items()
                               if not k[0].startswith("fwd_")}
         if "pytorch_layers_elapsed" in e:
@@ -875,9 +949,10 @@ def main():
         t_ = res["train"]
         ms = t_["elapsed"] * 1e3 / a.steps
         line.update({"train_step_ms": round(ms, 3), "train_videos_per_s": round(world * B * a.steps / t_["elapsed"], 3),
-                     "train_last_timed_step_loss": t_.get("last_loss"),
-                     "train_roofline": bwd_roofline(t_["ktimes"]), "train_graphs": t_["graphs"],
+                     "train_last_timed_step_loss": t_.get("last_loss"), "train_graphs": t_["graphs"],
                      "train_seconds_per_rank": [round(x, 4) for x in t_["per_rank"]]})
+        if a.full:
+            line["train_roofline"] = bwd_roofline(t_["ktimes"])
         if t_.get("exchange_ms"):
             # the eager gradient exchange between the captured graphs (rank 0's view): total = first bucket posted -> all
             # buckets reduced, exposed = the part that is not hidden under the encoder's backward
@@ -887,21 +962,24 @@ def main():
         kernels_us["train"] = {ktag(k): {"us": round(v[0], 2), "n": v[1]} for k, v in t_["ktimes"].items()}
         if "eval" not in res:
             line.update({"metric": "train-step ms", "value": round(ms, 3), "unit": "ms", "ms_per_step": round(ms, 3),
-                         "higher_is_better": False, "roofline": line["train_roofline"]})
-    line["kernels_us"] = kernels_us
-    line["shader_clock_mhz"] = {"after_eval_timed_region": (res.get("eval") or {}).get("clock_mhz"),
-                                "after_train_timed_region_and_instrumented_steps": (res.get("train") or {}).get("clock_mhz"),
-                                "note": "gvl_clock_probe: cycle counter against the 100 MHz wall clock over a chain of dependent "
-                                        "FMAs queued right behind the region (MI355X max 2400)"}
-    if line.get("roofline") is not None and rank == 0 and a.T != 512 and a.dtype == "f32" and "eval" in res and not a.no_probes:
+                         "higher_is_better": False})
+            if a.full:
+                line["roofline"] = line["train_roofline"]
+    if a.full:
+        line["kernels_us"] = kernels_us
+        line["shader_clock_mhz"] = {"after_eval_timed_region": (res.get("eval") or {}).get("clock_mhz"),
+                                    "after_train_timed_region_and_instrumented_steps": (res.get("train") or {}).get("clock_mhz"),
+                                    "note": "gvl_clock_probe: cycle counter against the 100 MHz wall clock over a chain of dependent "
+                                            "FMAs queued right behind the region (MI355X max 2400)"}
+    if a.full and line.get("roofline") is not None and rank == 0 and a.T != 512 and a.dtype == "f32" and "eval" in res and not a.no_probes:
         line["roofline"]["cfg_L_launch"] = kernel_probe(dev, B)
         line["roofline"]["B64_launch"] = kernel_probe(dev, 64, T=a.T, Q=a.queries)
         line["roofline"]["B256_launch"] = kernel_probe(dev, 256, T=a.T, Q=a.queries)      # latency-free sweep 16 / 64 / 256
-    if line.get("train_roofline") is not None and rank == 0 and a.T != 512 and a.dtype == "f32" and not a.no_probes:
+    if a.full and line.get("train_roofline") is not None and rank == 0 and a.T != 512 and a.dtype == "f32" and not a.no_probes:
         line["train_roofline"]["cfg_L_launch"] = kernel_probe(dev, B, backward=True)
         line["train_roofline"]["B64_launch"] = kernel_probe(dev, 64, T=a.T, Q=a.queries, backward=True)
         line["train_roofline"]["B256_launch"] = kernel_probe(dev, 256, T=a.T, Q=a.queries, backward=True)
-    if rank == 0 and "eval" in res and not a.no_captioner and a.dtype == "f32" and not a.no_probes:
+    if a.full and rank == 0 and "eval" in res and not a.no_captioner and a.dtype == "f32" and not a.no_probes:
         with torch.no_grad():
             lib = gemm_probe(model, dev, B * a.queries)
         head = model.caption_head[-1]
@@ -931,7 +1009,7 @@ def main():
                 "fp32_library_gemm_same_shape": lib}
         else:
             line["dominant_library_gemm"] = lib
-    if rank == 0 and world == 1 and not a.no_probes and not a.no_graph and a.dtype == "f32":
+    if a.full and rank == 0 and world == 1 and not a.no_probes and not a.no_graph and a.dtype == "f32":
         # the same kernels' durations INSIDE the replayed graphs, from a rocprofv3 kernel trace of a short child run of this script
         # (the eager stamps above read 3-10 % shorter than the launches the timed region actually replays)
         ig = in_graph_kernel_us(a, "both" if ("eval" in res and "train" in res) else ("eval" if "eval" in res else "train"))
@@ -947,8 +1025,10 @@ def main():
                 blk["in_graph_launches"] = got
             else:
                 blk["in_graph_note"] = ig.get("error") if isinstance(ig, dict) else str(ig)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and "eval" in res:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and "eval" in res:
         line["cpu_baseline"] = cpu_baseline(model, opt, a.T)
+    if rank == 0 and a.dump_outputs:
+        write_outputs(dumped, a.dump_outputs)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:

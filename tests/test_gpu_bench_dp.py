@@ -53,8 +53,8 @@ def _run_ranks(world, mode, launcher):
         head = ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
                  "127.0.0.1", "--master-port", str(_free_port())] if launcher else [sys.executable])
         cmd = head + [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps",
-                      "3", "--warmup", "1", "--batch", "4", "--queries", "40", "--rotate", "3", "--no-cpu-baseline",
-                      "--no-probes"] + (["--mode", "train"] if mode == "train" else []) + (
+                      "3", "--warmup", "1", "--batch", "4", "--queries", "40", "--rotate", "3", "--full",
+                      "--no-cpu-baseline", "--no-probes"] + (["--mode", "train"] if mode == "train" else []) + (
                           [] if launcher else ["--launch-timeout", "280" if world == 2 else "560"])
         proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=ROOT,
                                 start_new_session=True)                  # own process group: a timeout takes the ranks too

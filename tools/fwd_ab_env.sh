@@ -6,8 +6,8 @@ alt="$1"
 python3 tools/fwd_phase_stamps.py 2>/dev/null | grep -v "^backward" > $out/stamps_shipped.txt
 env $alt python3 tools/fwd_phase_stamps.py 2>/dev/null | grep -v "^backward" > $out/stamps_alt.txt
 for k in 1 2 3; do
-  env $alt python3 bench.py --mode eval --no-cpu-baseline --no-probes --steps 30 --warmup 5 2>/dev/null | tail -1 > $out/alt_$k.json
-  python3 bench.py --mode eval --no-cpu-baseline --no-probes --steps 30 --warmup 5 2>/dev/null | tail -1 > $out/shipped_$k.json
+  env $alt python3 bench.py --full --mode eval --no-cpu-baseline --no-probes --steps 30 --warmup 5 2>/dev/null | tail -1 > $out/alt_$k.json
+  python3 bench.py --full --mode eval --no-cpu-baseline --no-probes --steps 30 --warmup 5 2>/dev/null | tail -1 > $out/shipped_$k.json
 done
 echo "---- shipped"; cat $out/stamps_shipped.txt
 echo "---- $alt"; cat $out/stamps_alt.txt

@@ -13,7 +13,7 @@ runs = {
 }
 out = {}
 for name, args in runs.items():
-    p = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--steps", "16"] + args, capture_output=True, text=True)
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--steps", "16"] + args, capture_output=True, text=True)
     try:
         d = json.loads(p.stdout.strip().splitlines()[-1])
         keep = {k: d.get(k) for k in ("value", "unit", "ms_per_step", "train_step_ms", "dtype", "config", "eval_graphs", "train_graphs")}

@@ -5,8 +5,8 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/r06p; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pe /tmp/pt
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt -- python3 $root/bench.py --mode train --no-cpu-baseline --no-probes --steps 20 --warmup 5 > $out/train_bench_line_under_rocprof.json 2> $out/train.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pe -- python3 $root/bench.py --mode eval --no-cpu-baseline --no-probes --steps 20 --warmup 5 > $out/eval_bench_line_under_rocprof.json 2> $out/eval.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt -- python3 $root/bench.py --full --mode train --no-cpu-baseline --no-probes --steps 20 --warmup 5 > $out/train_bench_line_under_rocprof.json 2> $out/train.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pe -- python3 $root/bench.py --full --mode eval --no-cpu-baseline --no-probes --steps 20 --warmup 5 > $out/eval_bench_line_under_rocprof.json 2> $out/eval.err
 cd $root
 python tools/step_timeline.py /tmp/pt k_advance_step --full > $out/train_timeline.txt 2>&1
 python tools/step_timeline.py /tmp/pe k_pyramid_geometry --full > $out/eval_timeline.txt 2>&1

@@ -5,5 +5,5 @@
 out=$PWD/gpurun_out/round_ab; mkdir -p $out
 for k in 1 2; do
   (cd _r4tree && python3 bench.py --no-cpu-baseline --steps 24 --warmup 3 2>/dev/null | tail -1) > $out/old_$k.json
-  python3 bench.py --no-cpu-baseline --steps 24 --warmup 3 2>/dev/null | tail -1 > $out/new_$k.json
+  python3 bench.py --full --no-cpu-baseline --steps 24 --warmup 3 2>/dev/null | tail -1 > $out/new_$k.json
 done
