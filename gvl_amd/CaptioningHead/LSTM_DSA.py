@@ -35,9 +35,6 @@ from ..linear import mirror_linear as _mirror_linear, mirror_linear_eligible as 
 from ..linear import Linear, split_gemm_enabled, split_linear, vocab_nll, vocab_nll_eligible
 
 
-_ATTEND_PRE = os.environ.get("GVL_ATTEND_PRE", "1") != "0"            # (A/B: the offsets' hidden-state product inside the attention kernel)
-_GREEDY_MERGED = os.environ.get("GVL_GREEDY_MERGED", "1") != "0"      # (A/B: h2att(h) as a launch of its own)
-
 class ShowAttendTellCore(nn.Module):
     def __init__(self, opt):
         super().__init__()
@@ -200,9 +197,7 @@ class ShowAttendTellCore(nn.Module):
         every call); the operands of the attention kernel stay fp32."""
         params = (self.deformable_att.sampling_offsets.weight, self.h2att.weight, self.h2att.bias, self.rnn.weight_hh_l0,
                   self.rnn.weight_ih_l0, self.alpha_net.weight)
-        cell_fused = os.environ.get("GVL_CELL_FUSED", "1") != "0"
-        gates_fused = cell_fused and os.environ.get("GVL_GATES_FUSED", "1") != "0"
-        key = tuple((p_.data_ptr(), p_._version) for p_ in params) + (split_gemm_enabled(), cell_fused, gates_fused, gemm_dtype)
+        key = tuple((p_.data_ptr(), p_._version) for p_ in params) + (split_gemm_enabled(), gemm_dtype)
         cache = self.__dict__.setdefault("_inf_w", {})
         if cache and next(iter(cache))[:-1] != key[:-1]:
             cache.clear()
@@ -219,28 +214,20 @@ class ShowAttendTellCore(nn.Module):
                 if (gemm_dtype == torch.float32 and split_gemm_enabled() and self.rnn_size % 32 == 0
                         and self.att_feat_size % 32 == 0):
                     # fp32 products on the fp16 matrix cores (gvl_gemm_f16x3_f32): the weight side is split once
-                    w_hh, w_att = self.rnn.weight_hh_l0, self.rnn.weight_ih_l0[:, E:E + self.att_feat_size]
-                    if cell_fused and self.rnn_size % 8 == 0:
-                        # the LSTM cell runs in the epilogue of the attention product (gvl_gemm_f16x3_lstm_f32): every
-                        # gate operand of the step is laid out as 4 unit + gate (GVL_CELL_FUSED=0: separate cell kernel)
-                        perm = w["gate_perm"] = MSDA.gate_permutation(self.rnn_size, w_hh.device)
-                        w_hh, w_att = w_hh[perm], w_att[perm]
+                    # the LSTM cell runs in the epilogue of the attention product (gvl_gemm_f16x3_lstm_f32): every
+                    # gate operand of the step is laid out as 4 unit + gate
+                    perm = w["gate_perm"] = MSDA.gate_permutation(self.rnn_size, self.rnn.weight_hh_l0.device)
+                    w_hh, w_att = self.rnn.weight_hh_l0[perm], self.rnn.weight_ih_l0[:, E:E + self.att_feat_size][perm]
                     w["w_h_cat_p"] = MSDA.split_rows(torch.cat([self.h2att.weight, w_hh], 0))
                     w["w_att_p"] = MSDA.split_rows(w_att.contiguous())
-                    if gates_fused and w.get("gate_perm") is not None:
-                        # BOTH halves of the gate product + the cell in one launch (gvl_gemm_f16x3_gates_f32: contraction
-                        # [h | att]); the product over h in front of the attention then only yields h2att(h).
-                        # GVL_GATES_FUSED=0: the (n, A + 4H) product + gates_h operand of round 4.
-                        w["w_gate_cat_p"] = MSDA.split_rows(torch.cat([w_hh, w_att], 1).contiguous())
-                        # ... and, as 16 more output columns, the hidden-state part of the sampling offsets
-                        # (gvl_cap_attend_pre_f32 then reads neither h nor that weight; GVL_ATTEND_PRE=0: the kernel's own product)
-                        if _ATTEND_PRE:
-                            w["w_h2att_p"] = MSDA.split_rows(torch.cat([self.h2att.weight, ow[:, :self.rnn_size]], 0).contiguous())
-                            w["b_h2att"] = torch.cat([self.h2att.bias.detach(), self.h2att.bias.new_zeros(ow.shape[0])])
-                            w["off_pre"] = True
-                        else:
-                            w["w_h2att_p"] = MSDA.split_rows(self.h2att.weight.contiguous())
-                            w["b_h2att"] = self.h2att.bias.detach().contiguous()
+                    # BOTH halves of the gate product + the cell in one launch (gvl_gemm_f16x3_gates_f32: contraction
+                    # [h | att]); the product over h in front of the attention then only yields h2att(h) ...
+                    w["w_gate_cat_p"] = MSDA.split_rows(torch.cat([w_hh, w_att], 1).contiguous())
+                    # ... and, as 16 more output columns, the hidden-state part of the sampling offsets
+                    # (gvl_cap_attend_pre_f32 then reads neither h nor that weight)
+                    w["w_h2att_p"] = MSDA.split_rows(torch.cat([self.h2att.weight, ow[:, :self.rnn_size]], 0).contiguous())
+                    w["b_h2att"] = torch.cat([self.h2att.bias.detach(), self.h2att.bias.new_zeros(ow.shape[0])])
+                    w["off_pre"] = True
             cache[key] = w
         return w
 
@@ -283,10 +270,8 @@ class ShowAttendTellCore(nn.Module):
                                       self.n_levels, self.n_points, planes=split, host_starts=const.get("host_starts"))
         if gates_one:                                                   # the recurrent operand travels as planes
             return att_res, (hp,)
-        if split and const.get("gate_perm") is not None:                # ... whose epilogue is the cell (step)
+        if split:                                                       # ... whose epilogue is the cell (step)
             return att_res, g_h
-        if split:                                                       # att_res arrives as the planes of the product
-            return MSDA.gemm_f16x3(att_res, const["w_att_p"]), g_h
         return torch.mm(att_res, const["w_att_t"]), g_h                 # (the hs part, gates_hs, is added in the cell)
 
     def attend_pre_ok(self, const, temporal_shapes):
@@ -319,8 +304,7 @@ class ShowAttendTellCore(nn.Module):
         if const.get("gate_perm") is not None:                          # g_x: planes of the attended feature (attend_part)
             return MSDA.gemm_f16x3_lstm(g_x, const["w_att_p"], g_h[:, self.att_hid_size:], const["gates_hs"], emb_gates,
                                         it, c)
-        return MSDA.lstm_cell(g_x, g_h[:, self.att_hid_size:], emb_gates, it, c, gates_c=const["gates_hs"],
-                              planes="w_h_cat_p" in const and g_x.dtype == torch.float32)
+        return MSDA.lstm_cell(g_x, g_h[:, self.att_hid_size:], emb_gates, it, c, gates_c=const["gates_hs"])
 
     def step(self, xt_gates, state, query, reference_points, temporal_shapes, level_start_index, const):
         """one token.  xt_gates = embed(it) @ W_ih[:, :E]^T  (B*Q, 4H)"""
@@ -699,14 +683,12 @@ class Captioner(nn.Module):
             fused = torch.is_grad_enabled() and self.core.fused_train_eligible(hs)
             # loss-only on the fused path: everything per token is laid out (steps, n, .) as the token loop keeps it, and the
             # few KB of ids / targets / weights are transposed instead of the 9-18 MB activations and gradients
-            tm = (fused and nll is not None and vocab_nll_eligible(hs, self.logit.weight, self.logit.bias)
-                  and os.environ.get("GVL_CAP_TIME_MAJOR", "1") != "0")
+            tm = fused and nll is not None and vocab_nll_eligible(hs, self.logit.weight, self.logit.bias)
             ids = seq[:, :steps].t() if tm else seq[:, :steps]
             from .. import layers as _layers
             emb = _layers.embed_rows(self.embed.weight, ids.reshape(-1)).view(*ids.shape, -1)
             mirror = self.core.__dict__.get("_gvl_wx_mirror")
-            if (mirror is not None and torch.is_grad_enabled() and os.environ.get("GVL_XT_MIRROR", "1") != "0"
-                    and _mirror_ok(emb, w_x, mirror)):
+            if mirror is not None and torch.is_grad_enabled() and _mirror_ok(emb, w_x, mirror):
                 # the embedding part of every token's gate pre-activations on the hand-written products (planes of W_ih's
                 # embedding columns: gvl_amd/train_planes.py register_mirror) instead of the fp32 library GEMMs
                 xt_all = _mirror_linear(emb, w_x, mirror)
@@ -843,13 +825,13 @@ class Captioner(nn.Module):
         if "h_planes_only" not in const:
             # every reader of h' in this loop takes its operand planes (the vocabulary product, h2att(h) + offsets, the next gate
             # product): the fp32 copy (a third of the gate kernel's stores) is then not written
-            const["h_planes_only"] = bool("w_off_h" in const and _GREEDY_MERGED and self.core.attend_pre_ok(const, st["tshapes"])
+            const["h_planes_only"] = bool("w_off_h" in const and self.core.attend_pre_ok(const, st["tshapes"])
                                           and self.core.gates_in_one_launch(st["h"], const)
                                           and self._logit_planes(st["h"]) is not None)
         for t in range(t0, t1):
             if t > 0:
                 hp = getattr(st["h"], "_gvl_planes", None)
-                if (t < T and hp is not None and _GREEDY_MERGED and isinstance(st["logits"], MSDA.GreedyPartials)
+                if (t < T and hp is not None and isinstance(st["logits"], MSDA.GreedyPartials)
                         and "w_off_h" in st["const"] and self.core.gates_in_one_launch(st["h"], st["const"])):
                     # the reduction of token t - 1 and h2att(h) of token t depend on different results of the last step: one launch
                     st["it"], st["h"]._gvl_h2att = MSDA.greedy_step_and_gemm(

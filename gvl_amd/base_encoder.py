@@ -3,7 +3,6 @@ pdvc/position_encoding.py:38-64.  Plain PyTorch-ROCm ops (conv1d / GroupNorm): S
 of hand-kernel scope (row f2 "next").  Parameter names: ``input_proj.{l}.{0,1}``, ``pos_embed.duration_embed_layer``.
 """
 import ctypes
-import os
 import math
 
 import torch
@@ -130,8 +129,7 @@ class _PyramidTrainFunction(torch.autograd.Function):
             fwd, _, bias = tp.lookup((mats[l],))
             y = torch.empty(a.shape[0], C, device=dev, dtype=torch.float32)
             op = Operand(fwd, C, a.shape[1], bias)
-            if (l > 0 and a.shape[0] <= 1024 and op.K <= 4096 and L.splitk_pays(a.shape[0], op.N, op.K)
-                    and os.environ.get("GVL_CONV_SPLITK", "1") != "0"):
+            if l > 0 and a.shape[0] <= 1024 and op.K <= 4096 and L.splitk_pays(a.shape[0], op.N, op.K):
                 L.linear_splitk(a, am, op, out=y, bias=True)          # (few rows of taps, contraction 3 C_in: as forward_flat)
             else:
                 L.linear(a, op, [L.seg(0, y, am)])
@@ -267,13 +265,11 @@ class BaseEncoder(nn.Module):
         return lengths
 
     def flat_train_eligible(self, vf, mask):
-        """the TRAINING forward of the pyramid on the hand-written kernels (_PyramidTrainFunction); GVL_TRAIN_PYRAMID=torch keeps
-        the PyTorch formulation (A/B switch)"""
-        import os
+        """the TRAINING forward of the pyramid on the hand-written kernels (_PyramidTrainFunction)"""
         from . import layers as L
         from . import linear as GL
         c0 = self.input_proj[0][0]
-        return (os.environ.get("GVL_TRAIN_PYRAMID", "") != "torch" and L.enabled() and GL.train_linear_enabled()
+        return (L.enabled() and GL.train_linear_enabled()
                 and torch.is_grad_enabled() and self.training and not torch.is_autocast_enabled()
                 and vf.is_cuda and vf.dtype == torch.float32 and 1 < self.num_feature_levels <= 8
                 and isinstance(c0, nn.Conv1d) and vf.shape[-1] % 64 == 0 and self.hidden_dim % 64 == 0
@@ -386,8 +382,7 @@ class BaseEncoder(nn.Module):
             am, _ = L.row_absmax(a)
             y = torch.empty(N * (t_out + 1), C, device=dev, dtype=torch.float32)
             w = self._conv_weights(l)
-            if (a.shape[0] <= 1024 and w.K <= 4096 and L.splitk_pays(a.shape[0], w.N, w.K)
-                    and os.environ.get("GVL_CONV_SPLITK", "1") != "0"):
+            if a.shape[0] <= 1024 and w.K <= 4096 and L.splitk_pays(a.shape[0], w.N, w.K):
                 # a few hundred rows of taps against a contraction of 3 C_in: 13-52 tiles of 48 K stages -- split over K.  (Not for
                 # thousands of rows per level -- long videos: their tiles fill the chip as they are -- nor for the 9216-long
                 # contraction of 3072-d features: the T = 512 parity test sits within 2 % of its tolerance and the partial sums'

@@ -71,7 +71,7 @@ OUT_DEV = os.path.join(ROOT, "tools", "_bin", "libgvl_msda_dev.so")     # (git-i
 
 
 def build_dev(sources, defs, verbose=False):
-    """Timing / ablation builds of single kernels (`tools/*_ablate.sh`, `*_stamps.sh`): the named source files compiled with `defs`
+    """Timing builds of single kernels (`tools/*_stamps.sh`, `tools/vocab_clocks.sh`): the named source files compiled with `defs`
     (-DGVL_...) into build/obj_dev, linked with the SHIPPED library's other objects into tools/_bin/libgvl_msda_dev.so -- the shipped
     library and its objects are never touched.  A process uses it through GVL_LIB_PATH (gvl_amd/_lib.py)."""
     objdir, devdir = os.path.join(ROOT, "build", "obj"), os.path.join(ROOT, "build", "obj_dev")
@@ -109,7 +109,7 @@ def build_dev(sources, defs, verbose=False):
 
 
 if __name__ == "__main__":
-    if "--dev" in sys.argv:                  # python -m gvl_amd.build --dev gvl_gemm16.hip -DGVL_V_NO_EPI ...
+    if "--dev" in sys.argv:                  # python -m gvl_amd.build --dev gvl_gemm16.hip -DGVL_V_CLOCKS ...
         rest = sys.argv[sys.argv.index("--dev") + 1:]
         print(build_dev([a for a in rest if not a.startswith("-")], [a for a in rest if a.startswith("-")], verbose=True))
     else:

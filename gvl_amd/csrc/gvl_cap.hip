@@ -789,29 +789,19 @@ int cap_attend_impl(const char *what, const ST *slab, const int64_t *shapes, con
       };
       return val2 ? go(k_cap_attend_lds<12, true, 8>) : go(k_cap_attend_lds<12, true, 12>);
     }
-    const char *e = gvl::env_str("GVL_CAP_LDS");
     // rows of levels 2, 3 (ctx2att half) and of level 3 (value half): known to the caller that passes host level starts
     const int n_ctx = lsi_host ? S - (int)lsi_host[2] : 0, n_val = lsi_host ? S - (int)lsi_host[3] : 0;
-    if (o_hi && L == 4 && P == 4 && lsi_host && n_val >= 1 && n_ctx >= n_val && n_ctx + n_val <= 63 &&
-        !(e && atoi(e) == 0)) {
+    if (o_hi && L == 4 && P == 4 && lsi_host && n_val >= 1 && n_ctx >= n_val && n_ctx + n_val <= 63) {
       // the coarse end of each video's slab in LDS (k_cap_attend_lds): 64 half rows of 2 KB beside the 32 KB offsets weight
       int parts = 32 / vids_per_group;                                 // workgroups per video: one per CU of the video's XCD
       parts = parts < 1 ? 1 : (parts > Q ? Q : parts);
       const size_t lds = (size_t)kLP * kC * sizeof(float) + (size_t)(n_ctx + n_val) * kC * sizeof(float);
-      const char *w = gvl::env_str("GVL_CAP_LDS_WAVES");
       const dim3 grid(8 * vids_per_group * parts);
-      if (w && atoi(w) == 8) {
-        if (int rc = gvl::ensure_lds(k_cap_attend_lds<8>, lds)) return rc;
-        return gvl::launch(GVL_PROF_CAP_ATTEND, B * Q, B, "k_cap_attend_lds", k_cap_attend_lds<8>, grid, dim3(8 * 64), lds,
-                           (hipStream_t)stream, slab, shapes, lsi, ref, off_hs, h, w_off_h, att_h, alpha_w, alpha_b, B, S, L,
-                           Q, P, RD, vids_per_group, parts, n_ctx, n_val, att_h_ld, (_Float16 *)o_hi, (_Float16 *)o_lo, o_scale,
-                           (const float *)nullptr, 0);
-      }
       if (int rc = gvl::ensure_lds(k_cap_attend_lds<12>, lds)) return rc;
       return gvl::launch(GVL_PROF_CAP_ATTEND, B * Q, B, "k_cap_attend_lds", k_cap_attend_lds<12>, grid, dim3(12 * 64), lds,
                          (hipStream_t)stream, slab, shapes, lsi, ref, off_hs, h, w_off_h, att_h, alpha_w, alpha_b, B, S, L, Q,
                          P, RD, vids_per_group, parts, n_ctx, n_val, att_h_ld, (_Float16 *)o_hi, (_Float16 *)o_lo, o_scale,
-                           (const float *)nullptr, 0);
+                         (const float *)nullptr, 0);
     }
   }
   const int rows_per_group = vids_per_group * Q;

@@ -130,11 +130,6 @@ __device__ __forceinline__ void lstm_loads(LstmPre &p, int cbase, int lane, cons
   const int gcol = cbase + 4 * u < N ? cbase + 4 * u : 0;              // first of this lane's unit's four gate columns
   const int H = le.H;
   p.cs = *reinterpret_cast<const float4 *>(Bs + gcol);
-#ifdef GVL_ABLATE_CELL_LOADS                                           /* timing-only build (tools/cell_ablate.sh) */
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { p.gh[k] = p.cs; p.gc[k] = p.cs; p.ge[k] = p.cs; p.cp[k] = p.cs.x; }
-  if (true) return;
-#endif
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     p.gh[k] = *reinterpret_cast<const float4 *>(le.gates_h + (int64_t)p.rowc[k] * le.ld_h + gcol);
@@ -166,12 +161,7 @@ __device__ __forceinline__ void lstm_finish(const LstmPre &p, const f16acc &am, 
     const float gi = a[0] + p.gh[k].x + p.ge[k].x, gf = a[1] + p.gh[k].y + p.ge[k].y, gg = a[2] + p.gh[k].z + p.ge[k].z,
                 go = a[3] + p.gh[k].w + p.ge[k].w;
     float cn, hn;
-#ifdef GVL_ABLATE_CELL_MATH                                            /* timing-only build */
-    cn = gi + gf + p.cp[k];
-    hn = gg + go;
-#else
     gvl_lstm_point(gi, gf, gg, go, p.cp[k], cn, hn);
-#endif
     // (h' as the fp32 number it is stored as: left to itself the compiler folds the last product of the cell into the
     //  fp16 conversions below -- v_fma_mixlo_f16 of the exact product -- and the planes no longer split h' itself)
     asm volatile("" : "+v"(hn));
@@ -533,13 +523,6 @@ __global__ void __launch_bounds__(512, 1)
 
   // fragments of one K half (16) of a stage: 8 ds_read_b128; the 12 MFMAs they feed
   auto frags = [&](const uint4 *st, int s, h8 (&ah)[2], h8 (&al)[2], h8 (&bh)[NJ], h8 (&bl)[NJ]) {
-#ifdef GVL_ABLATE_LDS                                                  // (timing-only build: operands from registers)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { ah[i] = __builtin_bit_cast(h8, make_uint4(fa[s], i, 2, 3)); al[i] = ah[i]; }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { bh[j] = __builtin_bit_cast(h8, make_uint4(fb[s], j, 6, 7)); bl[j] = bh[j]; }
-    if (true) return;
-#endif
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       ah[i] = *reinterpret_cast<const h8 *>(&st[fa[s] + 128 * i]);
@@ -589,7 +572,6 @@ __global__ void __launch_bounds__(512, 1)
     h8 q_ah[2], q_al[2], q_bh[NJ], q_bl[NJ];                          // second K half
     frags(st, 1, q_ah, q_al, q_bh, q_bl);
     mfma12(p_ah, p_al, p_bh, p_bl);
-#ifndef GVL_NO_SCHED_GROUPS
     // (4 + 2 NJ) fragment reads of the next half between the 6 NJ MFMAs of this one
     if constexpr (!X1) {
 #pragma unroll
@@ -606,23 +588,17 @@ __global__ void __launch_bounds__(512, 1)
       }
       __builtin_amdgcn_sched_group_barrier(0x100, 2 - NJ, 0);
     }
-#endif
     // the next stage has landed (this wavefront's part; the barrier makes it everybody's); the one after stays in flight
     wait_vmcnt<kDma>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // my reads of this stage are complete
-#ifndef GVL_ABLATE_BARRIER
     __builtin_amdgcn_s_barrier();
-#endif
     asm volatile("" ::: "memory");
-#ifndef GVL_ABLATE_DMA                                                 // (tools/gemm16_ablate.sh: timing-only builds)
     {
       const bool over = kt + 3 >= KT;                                 // the stage three ahead belongs to the next tile
       issue(over ? tm2 : tm, over ? tn2 : tn, (over ? kt + 3 - KT : kt + 3) * kBK, buf);
     }
-#endif
     frags(smem + nbuf * kStageSlots, 0, p_ah, p_al, p_bh, p_bl);     // (stage 0 of the next tile at a tile's end)
     mfma12(q_ah, q_al, q_bh, q_bl);
-#ifndef GVL_NO_SCHED_GROUPS
     if constexpr (X1) {                                                // kDma DMA, 2 + NJ reads, 2 NJ MFMAs
 #pragma unroll
       for (int g = 0; g < 2 * NJ; ++g) {
@@ -652,7 +628,6 @@ __global__ void __launch_bounds__(512, 1)
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       }
     }
-#endif
     buf = nbuf;
     if constexpr (kPrefetch) {
       // the cell's operands are requested while the tile's last stages run: tokens and row scales four stages before
@@ -731,8 +706,7 @@ __device__ __forceinline__ void epilogue16(f4acc4 (&acc_m)[4][4], f4acc4 (&acc_x
     for (int r = 0; r < 4; ++r) rs[i][r] = As[min(row0 + 16 * i + 4 * fq + r, R - 1)];
   static_assert(EPI == kArgmax, "the 16 x 16 x 32 form serves the argmax epilogue (its stores would be 64-byte segments)");
   // The arithmetic below is NOT hidden behind the matrix cores -- all eight wavefronts reach it together -- and cost 15 us of
-  // the 120-130 us vocabulary product when written value by value as (compare + two selects, subtract + exp, guarded add;
-  // timing-only build GVL_ABLATE_EPI).  Per value now: 2 FMAs (logit), 1/2 v_max3 (column maximum FIRST, across the four
+  // the 120-130 us vocabulary product when written value by value as (compare + two selects, subtract + exp, guarded add).  Per value now: 2 FMAs (logit), 1/2 v_max3 (column maximum FIRST, across the four
   // lanes of the column too, so that no partial sum is ever rescaled), 1 FMA + v_exp (2^(v log2e - max log2e)), 1 add, and
   // compare + select for the index of the first maximum; the row < R guards only in the last row tile (wavefront-uniform).
   {
@@ -750,15 +724,6 @@ __device__ __forceinline__ void epilogue16(f4acc4 (&acc_m)[4][4], f4acc4 (&acc_x
       float best = -INFINITY, sum = 0.f;
       int arg = 0x7fffffff;
       float v[4][4];
-#ifdef GVL_ABLATE_EPI                                                  /* timing-only build: what the epilogue's arithmetic costs */
-      best = cs;                                                       /* (every accumulator stays live: 32 adds) */
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) best += acc_m[i][j][r] + acc_x[i][j][r];
-      sum = rs[0][0] + rb[1][1];
-      arg = row0;
-#else
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -782,7 +747,6 @@ __device__ __forceinline__ void epilogue16(f4acc4 (&acc_m)[4][4], f4acc4 (&acc_x
             arg = v[i][r] == best ? row0 + 16 * i + 4 * fq + r : arg;
           }
       }
-#endif
 #pragma unroll
       for (int o = 16; o <= 32; o <<= 1) {
         sum += __shfl_xor(sum, o);
@@ -849,11 +813,6 @@ __global__ void __launch_bounds__(512, 1)
   const int fa = lds_slot16(wm + (lane & 15), lane >> 4), fb = 2 * kASlots + lds_slot16(wn + (lane & 15), lane >> 4);
   struct Frag { h8 h[2], l[2]; };                                      // two 16-row blocks, hi | lo
   auto rdA = [&](const uint4 *st, int i0, Frag &f) {
-#ifdef GVL_ABLATE_LDS                                                  /* timing-only build: operand fragments from registers */
-#pragma unroll
-    for (int u = 0; u < 2; ++u) { f.h[u] = __builtin_bit_cast(h8, make_uint4(fa, i0 + u, 2, 3)); f.l[u] = f.h[u]; }
-    if (true) return;
-#endif
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       f.h[u] = *reinterpret_cast<const h8 *>(&st[fa + 64 * (i0 + u)]);
@@ -861,11 +820,6 @@ __global__ void __launch_bounds__(512, 1)
     }
   };
   auto rdB = [&](const uint4 *st, int j0, Frag &f) {
-#ifdef GVL_ABLATE_LDS
-#pragma unroll
-    for (int u = 0; u < 2; ++u) { f.h[u] = __builtin_bit_cast(h8, make_uint4(fb, j0 + u, 6, 7)); f.l[u] = f.h[u]; }
-    if (true) return;
-#endif
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       f.h[u] = *reinterpret_cast<const h8 *>(&st[fb + 64 * (j0 + u)]);
@@ -925,21 +879,12 @@ __global__ void __launch_bounds__(512, 1)
   rdA(smem, 0, a01);
   rdB(smem, 0, bX);
   int buf = 0, kt = 0;
-  // (timing-only builds, tools/m16_ablate.sh: GVL_ABLATE_BARRIER / GVL_ABLATE_DMA drop the stage barrier / the operand DMA)
-#ifdef GVL_ABLATE_BARRIER
-#define GVL_M16_BARRIER()
-#else
 #define GVL_M16_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
-#ifdef GVL_ABLATE_DMA
-#define GVL_M16_ISSUE()
-#else
 #define GVL_M16_ISSUE()                                                                                              \
   {                                                                                                                  \
     const bool over = kt + 3 >= KT;                                                                                  \
     issue(over ? tm2 : tm, over ? tn2 : tn, (over ? kt + 3 - KT : kt + 3) * kBK, buf);                               \
   }
-#endif
   // one K stage: bA holds its columns 0-1 on entry, bB receives columns 2-3 and then the NEXT stage's columns 0-1
 #define GVL_STAGE(bA, bB)                                                                                           \
   {                                                                                                                  \
@@ -1039,16 +984,6 @@ __device__ __forceinline__ void epilogue_v(f4acc4 (&acc)[4][NJ], int row0, int c
     float best = -INFINITY, sum = 0.f;
     int arg = 0x7fffffff;
     float v[4][4];
-#ifdef GVL_V_NO_EPI                                                    /* timing-only build: every accumulator stays live, 16 adds */
-    best = cs;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) best += acc[i][j][r];
-    sum = rs[0][0] + rb[1][1];
-    arg = row0;
-    (void)v; (void)full; (void)kLog2e;
-#else
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1070,7 +1005,6 @@ __device__ __forceinline__ void epilogue_v(f4acc4 (&acc)[4][NJ], int row0, int c
           arg = v[i][r] == best ? row0 + 16 * i + 4 * fq + r : arg;
         }
     }
-#endif
 #pragma unroll
     for (int o = 16; o <= 32; o <<= 1) {
       sum += __shfl_xor(sum, o);
@@ -1113,11 +1047,6 @@ __global__ void __launch_bounds__(512, 1)
   int tm2, tn2;
   bool has_next = tile_of(vb + (int)gridDim.x, tiles_m, tiles_n, tm2, tn2);
   if (!has_next) { tm2 = tm; tn2 = tn; }
-#ifdef GVL_V_SAME_SRC                                                   /* timing-only: every unit re-fetches the plane's first KiB */
-#define GVL_V_SRC(X) (lane_off + 0u * (X))
-#else
-#define GVL_V_SRC(X) (X)
-#endif
   // unit I of the K stage at k0 of tile (tm_, tn_) -> stage buffer st
 #define GVL_V_DMA(I, TM, TN, K0, ST)                                                                                 \
   {                                                                                                                  \
@@ -1130,7 +1059,7 @@ __global__ void __launch_bounds__(512, 1)
     if (!(X1 && lo))                                                                                                 \
       __builtin_amdgcn_raw_ptr_buffer_load_lds(isA ? (lo ? rs_al : rs_ah) : (lo ? rs_bl : rs_bh),                    \
                                                (__attribute__((address_space(3))) void *)((ST) + dst), 16,           \
-                                               GVL_V_SRC(lane_off + soff), 0, 0, 0);                                 \
+                                               lane_off + soff, 0, 0, 0);                                            \
   }
 
   f4acc4 acc[4][NJ];
@@ -1142,8 +1071,6 @@ __global__ void __launch_bounds__(512, 1)
   const int fa = lds_slot16(wa + (lane & 15), lane >> 4), fb = 2 * kASlots + lds_slot16(wb + (lane & 15), lane >> 4);
   h8 ah[4], al[4], bh[4], bl[4];
   const _Float16 k2048 = (_Float16)2048.f;
-  // (timing-only builds, tools/vocab_ablate.sh: GVL_V_NO_DMA / GVL_V_NO_BARRIER / GVL_V_NO_EPI drop the operand DMA / the stage
-  //  barrier / the epilogue's arithmetic)
 #define GVL_V_RDA(ST, I)                                                                                             \
   {                                                                                                                  \
     ah[I] = *reinterpret_cast<const h8 *>(&(ST)[fa + 64 * (I)]);                                                     \
@@ -1154,28 +1081,16 @@ __global__ void __launch_bounds__(512, 1)
     bh[S] = *reinterpret_cast<const h8 *>(&(ST)[fb + 64 * (J)]);                                                     \
     if constexpr (!X1) bl[S] = *reinterpret_cast<const h8 *>(&(ST)[kBSlots + fb + 64 * (J)]);                        \
   }
-#ifdef GVL_V_NO_VMWAIT
-#define GVL_V_WAIT() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
 #define GVL_V_WAIT() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
-#endif
-#ifdef GVL_V_NO_BARRIER
-#define GVL_V_BARRIER()
-#else
 #define GVL_V_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
   // the units of a stage's DMA are issued over seven B blocks: units 0-3 under blocks 8, 9 of the stage BEFORE the one that runs
   // while they land (AHEAD = 2: into the buffer the barrier has just freed), units 4-8 under blocks 0-2 of that stage (AHEAD = 1)
-#if defined(GVL_V_NO_DMA) || defined(GVL_V_DMA_ONCE)                    /* ONCE: both buffers filled before the loop, then none */
-#define GVL_V_ISSUE(P, I, AHEAD, ST)
-#else
 #define GVL_V_ISSUE(P, I, AHEAD, ST)                                                                                 \
   {                                                                                                                  \
     const int kn = kt + (P) + (AHEAD);                                                                               \
     const bool over = kn >= KT;                                                                                      \
     GVL_V_DMA(I, over ? tm2 : tm, over ? tn2 : tn, (over ? kn - KT : kn) * kBK, ST)                                  \
   }
-#endif
 #define GVL_V_MFMA3(I, J, BS, S)                                                                                     \
   {                                                                                                                  \
     acc[I][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[I], BS, acc[I][J], 0, 0, 0);                               \
@@ -1237,21 +1152,12 @@ __global__ void __launch_bounds__(512, 1)
   {                                                                    // stage 0 whole, units 0-3 of stage 1
     constexpr int P = 0;
     kt = -2;                                                           // (GVL_V_ISSUE adds P + AHEAD)
-#ifdef GVL_V_DMA_ONCE
-#define GVL_V_ISSUE0(I, ST) GVL_V_DMA(I, tm, tn, (kt + 2) * kBK, ST)
-#else
 #define GVL_V_ISSUE0(I, ST) GVL_V_ISSUE(P, I, 2, ST)
-#endif
     GVL_V_ISSUE0(0, smem) GVL_V_ISSUE0(1, smem) GVL_V_ISSUE0(2, smem) GVL_V_ISSUE0(3, smem) GVL_V_ISSUE0(4, smem)
     GVL_V_ISSUE0(5, smem) GVL_V_ISSUE0(6, smem) GVL_V_ISSUE0(7, smem) GVL_V_ISSUE0(8, smem)
     kt = -1;
     GVL_V_ISSUE0(0, smem + kStageSlots) GVL_V_ISSUE0(1, smem + kStageSlots) GVL_V_ISSUE0(2, smem + kStageSlots)
     GVL_V_ISSUE0(3, smem + kStageSlots)
-#ifdef GVL_V_DMA_ONCE
-    GVL_V_ISSUE0(4, smem + kStageSlots) GVL_V_ISSUE0(5, smem + kStageSlots) GVL_V_ISSUE0(6, smem + kStageSlots)
-    GVL_V_ISSUE0(7, smem + kStageSlots) GVL_V_ISSUE0(8, smem + kStageSlots)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 #undef GVL_V_ISSUE0
     kt = 0;
   }
@@ -1305,7 +1211,6 @@ __global__ void __launch_bounds__(512, 1)
 #undef GVL_V_RDB
 #undef GVL_V_RDA
 #undef GVL_V_DMA
-#undef GVL_V_SRC
 }
 
 // ---- k_gates_f16x3: BOTH halves of the LSTM gate product of a token step in one launch, the cell applied (round 5).
@@ -1728,18 +1633,12 @@ int persistent_grid(int tiles) {
       n = 256;
     cus = n / 8 * 8 > 0 ? n / 8 * 8 : 8;
   }
-  const char *e = gvl::env_str("GVL_GEMM16_GRID");                    // (experiments: 0 = one workgroup per tile)
   const int padded = (tiles + 7) / 8 * 8;
-  if (e && atoi(e) == 0) return padded;
   return padded < cus ? padded : cus;
 }
 
-// the 16 x 16 x 32 form (two K stages per loop iteration: K % 64 == 0, at least four stages); GVL_GEMM16_MFMA=32 keeps
-// the 32 x 32 x 16 kernels for A/B runs
-bool use_m16(int K) {
-  const char *e = gvl::env_str("GVL_GEMM16_MFMA");
-  return !(e && atoi(e) == 32) && K % 64 == 0 && K >= 128;
-}
+// the 16 x 16 x 32 form (two K stages per loop iteration: K % 64 == 0, at least four stages)
+bool use_m16(int K) { return K % 64 == 0 && K >= 128; }
 
 // GVL_VOCAB_FORM: "m16" keeps k_gemm_f16x3_m16 for the vocabulary product, "v" takes k_vocab_f16x3 wherever it applies (A/B
 // runs, tests)
@@ -1806,8 +1705,7 @@ extern "C" int gvl_gemm_f16x3_f32(const void *a_hi, const void *a_lo, const floa
                          dim3(persistent_grid(tiles_m * tiles_n)), dim3(512), 0, (hipStream_t)stream, ah, al, a_scale, bh,
                          bl, b_scale, bias, R, N, K, out, ldo, tiles_m, tiles_n, LstmEpi{});
     }
-    const char *mid_min = gvl::env_str("GVL_GEMM16_MID_MIN");          // (experiments: the fewest 128 x 128 tiles that take this form)
-    if (t_mid >= (mid_min ? atoi(mid_min) : 384) && !gvl::env_str("GVL_GEMM16_NO_MID")) {
+    if (t_mid >= 384) {
       const int tiles_m = (R + 127) / 128, tiles_n = (N + 127) / 128;
       return gvl::launch(GVL_PROF_GEMM16, R, N, "k_gemm_f16x3_w8", (x1 ? k_gemm_f16x3_w8<2, 4, 1, kStore, true> : k_gemm_f16x3_w8<2, 4, 1, kStore, false>),
                          dim3(persistent_grid(tiles_m * tiles_n)), dim3(512), 0, (hipStream_t)stream, ah, al, a_scale, bh,
@@ -1853,7 +1751,7 @@ extern "C" int gvl_gemm_f16x3_lstm_f32(const void *a_hi, const void *a_lo, const
                          dim3(persistent_grid(tiles_m * tiles_n)), dim3(512), 0, (hipStream_t)stream, ah, al, a_scale, bh,
                          bl, w_scale, (const float *)nullptr, R, N, K, (float *)nullptr, (int64_t)0, tiles_m, tiles_n, le);
     }
-    if (t_mid >= 384 && !gvl::env_str("GVL_GEMM16_NO_MID")) {
+    if (t_mid >= 384) {
       const int tiles_m = (R + 127) / 128, tiles_n = (N + 127) / 128;
       return gvl::launch(GVL_PROF_GEMM16, R, N, "k_gemm_f16x3_w8<lstm>", (x1 ? k_gemm_f16x3_w8<2, 4, 1, kLstm, true> : k_gemm_f16x3_w8<2, 4, 1, kLstm, false>),
                          dim3(persistent_grid(tiles_m * tiles_n)), dim3(512), 0, (hipStream_t)stream, ah, al, a_scale, bh,
@@ -1917,8 +1815,7 @@ extern "C" int gvl_gemm_f16x3_argmax_f32(const void *x_hi, const void *x_lo, con
   const _Float16 *xh = (const _Float16 *)x_hi, *xl = (const _Float16 *)x_lo, *wh = (const _Float16 *)w_hi,
                  *wl = (const _Float16 *)w_lo;
   const int tiles_m = (V + kBM - 1) / kBM;                            // 128 vocabulary entries per tile, either form
-  const char *aform = gvl::env_str("GVL_ARGMAX_FORM");                // (4: the four-wavefront kernel, A/B runs)
-  if (R >= 1024 && K >= 3 * kBK && !(aform && atoi(aform) == 4)) {
+  if (R >= 1024 && K >= 3 * kBK) {
     const int tiles_n = (R + 255) / 256;
     if (use_m16(K)) {
       // 256 x 320 tiles with one accumulator (k_vocab_f16x3) when their rounds over the chip cost less than the 128 x 256

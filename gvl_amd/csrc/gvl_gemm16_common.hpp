@@ -97,17 +97,6 @@ __device__ __forceinline__ void mfma_stage(const uint4 *st, int a_lo_off, int b_
                                            const int (&fb)[NJ][2], f16acc (&acc_m)[2][NJ], f16acc (&acc_x)[2][NJ]) {
   // all fragment reads of the stage first: the second K half lands under the MFMAs of the first
   h8 f_ah[2][2], f_al[2][2], f_bh[2][NJ], f_bl[2][NJ];
-#ifdef GVL_ABLATE_LDS
-  st = reinterpret_cast<const uint4 *>(__builtin_assume_aligned(st, 16));
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { f_ah[s][i] = __builtin_bit_cast(h8, make_uint4(fa[i][s], 1, 2, 3)); f_al[s][i] = f_ah[s][i]; }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { f_bh[s][j] = __builtin_bit_cast(h8, make_uint4(fb[j][s], 5, 6, 7)); f_bl[s][j] = f_bh[s][j]; }
-  }
-  if (false)
-#endif
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
 #pragma unroll

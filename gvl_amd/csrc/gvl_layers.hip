@@ -1494,7 +1494,6 @@ extern "C" int gvl_linear_f16x3_f32(const float *a, int64_t lda, const float *a2
         if (t_ <= 256 && t_ > best) { best = t_; bm = cand; }
       }
   }
-  if (gvl::env_int("GVL_LIN_TILE", 0) == 64) wide = false;
   const int bn = wide ? 128 : kLinBN;
   p.tiles_m = (R + bm - 1) / bm; p.tiles_n = N / bn;
   p.xcd_cols = (flags & GVL_LIN_XCD_COLUMNS) && p.tiles_n >= 8;
@@ -1599,10 +1598,10 @@ extern "C" int gvl_layer_norm_rows_f32(const float *x, int R, int C, const float
   if (!x || !gamma || !beta || !y || (pos && pos_rows <= 0)) return fail(GVL_EINVAL, "gvl_layer_norm_rows_f32: null pointer");
   if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y | (uintptr_t)pos) & 15)
     return fail(GVL_EINVAL, "gvl_layer_norm_rows_f32: operands must be 16-byte aligned");
-  const int xcd_rows = gvl::env_int("GVL_ROWS_XCD", 1);   // (0: workgroup b = rows 4 b ..: A/B runs; tools/xcd_rows_probe.py: 28.8 -> 26.9 us for LN + 4800 x 512 x 512 product)
-  const int nb = (R + 3) / 4, grid = xcd_rows ? 8 * ((nb + 7) / 8) : nb;
+  // row groups by XCD (k_ln_rows: xcd_rows = 1): 28.8 -> 26.9 us for LN + 4800 x 512 x 512 product against workgroup b = rows 4 b ..
+  const int nb = (R + 3) / 4, grid = 8 * ((nb + 7) / 8);
   return gvl::launch(GVL_PROF_LAYER_NORM, R, C, "k_ln_rows", k_ln_rows, dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
-                     R, C, gamma, beta, eps, pos, pos ? pos_rows : 1, y, amax_y, amax_ypos, xcd_rows);
+                     R, C, gamma, beta, eps, pos, pos ? pos_rows : 1, y, amax_y, amax_ypos, 1);
 }
 
 extern "C" int gvl_row_absmax_f32(const float *x, int64_t ldx, int R, int C, const float *pos, int64_t ldp, int pos_rows,

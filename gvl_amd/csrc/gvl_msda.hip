@@ -251,12 +251,8 @@ __device__ inline float row_bcast_f(float v) { return dpp_f<0x150 + SRC>(v); }
 typedef float f2v __attribute__((ext_vector_type(2)));
 template <int SRC>
 __device__ inline f2v row_bcast_f2(f2v v) {
-#ifdef GVL_BCAST_2X32   // timing build: two 32-bit broadcasts instead of one 64-bit
-  return (f2v){row_bcast_f<SRC>(v.x), row_bcast_f<SRC>(v.y)};
-#else
   const long long r = __builtin_amdgcn_update_dpp((long long)0, __builtin_bit_cast(long long, v), 0x150 + SRC, 0xF, 0xF, true);
   return __builtin_bit_cast(f2v, r);
-#endif
 }
 // lane SRC's v broadcast over its row and added to this lane's `addend`, in ONE VALU instruction (v_add_u32_dpp).  The
 // compiler's DPP combiner does not fold the v_mov_dpp + v_add pair of the forward sample step (the broadcast is
@@ -289,23 +285,6 @@ __device__ inline void fma4x2(f2v c, const float4 &v0, const float4 &v1, f2v &a0
   a01 = __builtin_elementwise_fma(hi, (f2v){v1.x, v1.y}, a01);
   a23 = __builtin_elementwise_fma(hi, (f2v){v1.z, v1.w}, a23);
 }
-// TIMING BUILDS ONLY (-DGVL_FWD_FMAC_DPP; measured in round 5 and not shipped): acc (4 channels) += c.x * v0 + c.y * v1 with
-// the coefficient taken from lane SRC of the DPP row INSIDE the multiply-add (v_fmac_f32_dpp: the VOP2 form carries a DPP
-// control on its first operand) -- 8 instructions per sample step instead of a 64-bit broadcast + 4 v_pk_fma_f32, the same
-// products in the same order.  The forward's sample loop went from 3.33 to 3.94 us in situ (tools/fwd_ab.sh): a DPP operand
-// costs the FMA more than the separate broadcast does.
-template <int SRC>
-__device__ inline void fma4x2_bcast(f2v c, const float4 &v0, const float4 &v1, f2v &a01, f2v &a23) {
-  float ax = a01.x, ay = a01.y, az = a23.x, aw = a23.y;
-  const float cl = c.x, ch = c.y;
-#define GVL_FMAC_DPP(ACC, COEF, VAL) \
-  asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(ACC) : "v"(COEF), "v"(VAL), "n"(SRC));
-  GVL_FMAC_DPP(ax, cl, v0.x) GVL_FMAC_DPP(ay, cl, v0.y) GVL_FMAC_DPP(az, cl, v0.z) GVL_FMAC_DPP(aw, cl, v0.w)
-  GVL_FMAC_DPP(ax, ch, v1.x) GVL_FMAC_DPP(ay, ch, v1.y) GVL_FMAC_DPP(az, ch, v1.z) GVL_FMAC_DPP(aw, ch, v1.w)
-#undef GVL_FMAC_DPP
-  a01 = (f2v){ax, ay};
-  a23 = (f2v){az, aw};
-}
 // all-reduce (sum) inside every 16-lane row
 __device__ inline float row_allsum(float v) {
   v += dpp_f<0xB1>(v);    // quad_perm [1,0,3,2]
@@ -322,13 +301,6 @@ __device__ inline float row_allsum(float v) {
 __device__ inline float row_reduce_scatter16(const float (&v)[16], int j) {
   float a8[8], a4[4], a2[2];
   const bool b1 = j & 2, b0 = j & 1;
-#ifdef GVL_RS16_SELECTS    // timing build: the select form of rounds 2-5 for all four levels
-  const bool b3 = j & 8, b2 = j & 4;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a8[i] = (b3 ? v[8 + i] : v[i]) + dpp_f<0x140>(b3 ? v[i] : v[8 + i]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) a4[i] = (b2 ? a8[4 + i] : a8[i]) + dpp_f<0x141>(b2 ? a8[i] : a8[4 + i]);
-#else
   // Levels 1 and 2 without selects: which half of the row keeps element i and which keeps element 8 + i (4 + i) is a matter of
   // WHOLE DPP banks (lanes 0-7 | 8-15, then banks {0, 2} | {1, 3}), so each output is two v_add_f32_dpp with complementary
   // bank masks -- the partner's copy of the same element added to the own one -- instead of two selects + move + add.
@@ -352,7 +324,6 @@ __device__ inline float row_reduce_scatter16(const float (&v)[16], int j) {
       : "=&v"(a4[0]), "=&v"(a4[1]), "=&v"(a4[2]), "=&v"(a4[3])
       : "v"(a8[0]), "v"(a8[1]), "v"(a8[2]), "v"(a8[3]), "v"(a8[4]), "v"(a8[5]), "v"(a8[6]), "v"(a8[7]));
 #undef GVL_RS_PAIR
-#endif
 #pragma unroll
   for (int i = 0; i < 2; ++i) a2[i] = (b1 ? a4[2 + i] : a4[i]) + dpp_f<0x1B>(b1 ? a4[i] : a4[2 + i]);
   return (b0 ? a2[1] : a2[0]) + dpp_f<0xB1>(b0 ? a2[0] : a2[1]);
@@ -596,7 +567,7 @@ __global__ void __launch_bounds__(1024) k_fwd_t1d_d64(const VT *__restrict__ val
   const int wg_id = (int)(blockIdx.y * gridDim.x + blockIdx.x);
   // diagnostics (gvl_msda_debug_stamps): 100 MHz wall-clock stamps per workgroup {start, slab staged, loop done}
   if (stamps && threadIdx.x == 0) stamps[wg_id * 4 + 0] = wall_clock64();
-  // (nchunk < 0: diagnostic A/B switch GVL_MSDA_XCD_PAIRS=0 -- the plain id -> slab map)
+  // (nchunk < 0: the plain id -> slab map, which the host no longer asks for)
   const int bm = nchunk < 0 ? (int)blockIdx.x : slab_of_block((int)blockIdx.x, BM), chunk = (int)blockIdx.y;
   int b, m;
   if (m_shift >= 0) { b = bm >> m_shift; m = bm & (M - 1); }
@@ -769,20 +740,12 @@ __global__ void __launch_bounds__(1024) k_fwd_t1d_d64(const VT *__restrict__ val
   // (Round 5, with prep() still inside the loop: requesting the reads of four steps together, two groups in flight, did not
   // help -- 4.52 -> 4.75 us in situ at 118 registers; 35 fewer VALU instructions per pass bought ~0.3 us; moving prep() under
   // the slab transfer 1.0 us.)
-#ifdef GVL_FWD_ABL_NO_LDS      // timing build (tools/fwd_ablate.sh): the sample steps without their LDS reads
-#define GVL_FWD_ROWS(ROW, V0, V1) { const float t_ = __builtin_bit_cast(float, (int)(uintptr_t)(ROW)); V0 = make_float4(t_, cc.x, t_, cc.y); V1 = V0; }
-#else
 #define GVL_FWD_ROWS(ROW, V0, V1) { V0 = lds_ld4(ROW); V1 = lds_ld4((ROW) + 256); }
-#endif
   auto run_pass = [&](const int roff, const f2v cc) {
     const int q = qb + tq;
     const bool act = q < q1;
     f2v a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
-#ifdef GVL_FWD_FMAC_DPP         // timing build, see fma4x2_bcast
-#define GVL_FWD_ACC(SI, V0, V1) fma4x2_bcast<SI>(cc, V0, V1, a01, a23);
-#else
 #define GVL_FWD_ACC(SI, V0, V1) fma4x2(row_bcast_f2<SI>(cc), V0, V1, a01, a23);
-#endif
 #define GVL_FWD_STEP(SI)                                                        \
   if (FULL16 || SI < LP) {                                                      \
     float4 v0, v1;                                                              \
@@ -795,7 +758,7 @@ __global__ void __launch_bounds__(1024) k_fwd_t1d_d64(const VT *__restrict__ val
     // is the guarded store, and the optimiser sinks the whole FMA chain of a pass into that guard -- behind all 32 reads.
     // Inside a group the compiler keeps two reads in flight.  Requesting a group's eight reads together was measured again
     // with prep() out of the loop (tools/fwd_ab.sh): loop 3.27 -> 3.41 us in situ.  Neither the LDS round trips nor the LDS
-    // bandwidth set the pass time: with the reads REMOVED (-DGVL_FWD_ABL_NO_LDS) the loop still takes 2.99 us -- it is the
+    // bandwidth set the pass time: with the reads REMOVED (a timing build) the loop still takes 2.99 us -- it is the
     // issue of the 64 v_pk_fma_f32 per wavefront pass plus 56 other vector instructions (two 32-bit broadcasts instead of
     // v_mov_b64_dpp: 3.21 -> 3.24 us; the broadcast folded into 128 v_fmac_f32_dpp: 3.33 -> 3.94 us).
 #define GVL_FWD_FENCE asm volatile("" : "+v"(a01), "+v"(a23) : : "memory"); __builtin_amdgcn_sched_barrier(0);
@@ -912,13 +875,7 @@ __device__ inline void gather8(const f2v tc, const char *G_b, int lane_off, f2v 
 #undef GVL_ACC
 }
 
-// LANE = SAMPLE own pass (round 6, GVL_BWD_LS; -DGVL_BWD_LS=0 is the lane = channels form of rounds 2-5).
-#ifndef GVL_BWD_LS
-#define GVL_BWD_LS 1
-#endif
-#ifndef GVL_BWD_LS_GROUP
-#define GVL_BWD_LS_GROUP 2
-#endif
+// LANE = SAMPLE own pass (round 6; the other instantiations keep the lane = channels form of rounds 2-5).
 // ------------------------------------------------------------------------------------------------------
 // The two dot products of ONE sample per lane -- g[q] . V[r_j] and g[q] . V[r_j + 1] over all 64 channels (round 6; shared by
 // the temporal backward kernels wherever the sample's rows are in LDS).  The query's grad_out row lives four channels per lane
@@ -940,7 +897,7 @@ __device__ __forceinline__ void ls_dot_pair(const float4 *slab4, const int row, 
       const int jo = j * 16;
       // (the column's offset travels by the same rotation as the channels: the direction of row_ror does not matter)
 #define GVL_ROR(K, V) ((K) == 0 ? (V) : dpp_f<(K) ? 0x120 + (K) : 0x121>(V))
-      // Software pipeline in groups of GVL_BWD_LS_GROUP steps: the rows of group n + 1 are requested before the products of
+      // Software pipeline in groups of two steps: the rows of group n + 1 are requested before the products of
       // group n are taken (left to itself the compiler requests two rows, waits for both, multiplies, and only then requests the
       // next two: sixteen exposed LDS round trips per pass with four wavefronts per SIMD to hide them).  The scheduling fences keep
       // the order; the waits the compiler inserts are counted ones (the newer group stays in flight).
@@ -957,16 +914,6 @@ __device__ __forceinline__ void ls_dot_pair(const float4 *slab4, const int row, 
     s1 = __builtin_elementwise_fma(bzw, (f2v){vb##K.z, vb##K.w}, s1);         \
   }
 #define GVL_LS_FENCE if constexpr (FENCED) __builtin_amdgcn_sched_barrier(0);
-#if GVL_BWD_LS_GROUP == 4
-      GVL_LS_ISSUE(0) GVL_LS_ISSUE(1) GVL_LS_ISSUE(2) GVL_LS_ISSUE(3) GVL_LS_FENCE
-      GVL_LS_ISSUE(4) GVL_LS_ISSUE(5) GVL_LS_ISSUE(6) GVL_LS_ISSUE(7) GVL_LS_FENCE
-      GVL_LS_USE(0) GVL_LS_USE(1) GVL_LS_USE(2) GVL_LS_USE(3) GVL_LS_FENCE
-      GVL_LS_ISSUE(8) GVL_LS_ISSUE(9) GVL_LS_ISSUE(10) GVL_LS_ISSUE(11) GVL_LS_FENCE
-      GVL_LS_USE(4) GVL_LS_USE(5) GVL_LS_USE(6) GVL_LS_USE(7) GVL_LS_FENCE
-      GVL_LS_ISSUE(12) GVL_LS_ISSUE(13) GVL_LS_ISSUE(14) GVL_LS_ISSUE(15) GVL_LS_FENCE
-      GVL_LS_USE(8) GVL_LS_USE(9) GVL_LS_USE(10) GVL_LS_USE(11) GVL_LS_FENCE
-      GVL_LS_USE(12) GVL_LS_USE(13) GVL_LS_USE(14) GVL_LS_USE(15) GVL_LS_FENCE
-#else
       GVL_LS_ISSUE(0) GVL_LS_ISSUE(1) GVL_LS_FENCE
       GVL_LS_ISSUE(2) GVL_LS_ISSUE(3) GVL_LS_FENCE GVL_LS_USE(0) GVL_LS_USE(1) GVL_LS_FENCE
       GVL_LS_ISSUE(4) GVL_LS_ISSUE(5) GVL_LS_FENCE GVL_LS_USE(2) GVL_LS_USE(3) GVL_LS_FENCE
@@ -976,7 +923,6 @@ __device__ __forceinline__ void ls_dot_pair(const float4 *slab4, const int row, 
       GVL_LS_ISSUE(12) GVL_LS_ISSUE(13) GVL_LS_FENCE GVL_LS_USE(10) GVL_LS_USE(11) GVL_LS_FENCE
       GVL_LS_ISSUE(14) GVL_LS_ISSUE(15) GVL_LS_FENCE GVL_LS_USE(12) GVL_LS_USE(13) GVL_LS_FENCE
       GVL_LS_USE(14) GVL_LS_USE(15) GVL_LS_FENCE
-#endif
 #undef GVL_LS_FENCE
 #undef GVL_LS_USE
 #undef GVL_LS_ISSUE
@@ -1110,7 +1056,7 @@ __global__ void __launch_bounds__(kBwdThreads) k_bwd_t1d_d64(const VT *__restric
       }
     }
     float d0, d1;
-    if constexpr (GVL_BWD_LS && FUSED && FULL16 && !L0G) {
+    if constexpr (FUSED && FULL16 && !L0G) {
       ls_dot_pair<false>(slab4, roff, g, j, d0, d1);      // one sample per lane (every row in LDS, sixteen samples per query)
     } else {
     // per sample the two dot products g . V[r], g . V[r+1]: every lane accumulates its 4-channel part for all 16
@@ -1444,7 +1390,7 @@ __global__ void __launch_bounds__(kBwdThreads) k_bwd_t1d_split(const VT *__restr
     // (the unfused instantiations keep lane = channels: with the plain loc / attn operands hipcc hoists all sixteen steps' row
     //  reads above the products and spills ~140 registers at the kernel's 128-register cap)
     float d0, d1;
-    if constexpr (GVL_BWD_LS && FUSED) {
+    if constexpr (FUSED) {
       ls_dot_pair<true>(slab4, roff, gq, j, d0, d1);
     } else {
 
@@ -1734,7 +1680,7 @@ __global__ void __launch_bounds__(kBwdThreads) k_bwd_t1d_own(const VT *__restric
     }
     __syncthreads();
     if (stamps && threadIdx.x == 0) stamps[blockIdx.x * 4 + 1] = wall_clock64();
-    if (dbg & 1) qb = q1;                                                  // diagnostics (GVL_MSDA_OWN_DEBUG): traffic of one phase alone
+    if (dbg & 1) qb = q1;                                                  // diagnostics: traffic of one phase alone
 #ifdef GVL_PHASE_TIMING   // dev build: cycles of the blocks of a pass (wave 0), summed over its passes
     long long tacc[5] = {0, 0, 0, 0, 0};
 #define GVL_T(K) { const long long t_ = __builtin_amdgcn_s_memtime(); tacc[K] += t_ - tprev; tprev = t_; }
@@ -1768,11 +1714,7 @@ __global__ void __launch_bounds__(kBwdThreads) k_bwd_t1d_own(const VT *__restric
       const float dylo = c.c_lo * c.dy * w, dyhi = c.c_hi * c.dy * w;
       GVL_T(0)                                                               // operand hand-over + coefficients
       float d0, d1;
-      if constexpr (false && GVL_BWD_LS && FUSED && !L0G) {   // (not here: the kernel sits at its register cap, +80 bytes of scratch)
-        ls_dot_pair<false>(slab4, roff - row0, gq, j, d0, d1);               // one sample per lane: every row is in LDS
-        GVL_T(1)
-        GVL_T(2)
-      } else {
+      // (lane = channels: ls_dot_pair's lane = sample form cost this kernel, at its register cap, 80 bytes of scratch)
       float p0[16], p1[16];
       // L0G: the eight level-0 rows of this pass are requested first and consumed last -- the twelve LDS steps run
       // while they travel
@@ -1834,7 +1776,6 @@ __global__ void __launch_bounds__(kBwdThreads) k_bwd_t1d_own(const VT *__restric
       d0 = row_reduce_scatter16(p0, j);
       d1 = row_reduce_scatter16(p1, j);
       GVL_T(2)                                                               // two reduce-scatters
-      }
       const float keep_w = fmaf(clo, d0, chi * d1);
       const float keep_x = fmaf(dxlo, d0, dxhi * d1);
       const float keep_y = fmaf(dylo, d0, dyhi * d1);
@@ -2110,8 +2051,7 @@ bool temporal_host(const int64_t *shapes_host, const int64_t *lsi_host, int L, i
   return run == S;
 }
 
-int pick_chunks(const char *env, int BM, int Q, int target_wgs) {
-  int n = env_int(env, 0);
+int pick_chunks(int n, int BM, int Q, int target_wgs) {             // n > 0: a chunk count asked for (tuning sweeps)
   if (n <= 0) n = (target_wgs + BM - 1) / BM;
   const int maxn = (Q + 15) / 16;   // keep >= 16 queries per workgroup
   if (n > maxn) n = maxn;
@@ -2125,9 +2065,8 @@ int run_fwd_t1d(const VT *value, const int64_t *shapes, const int64_t *lsi, cons
                 int S, int M, int L, int Q, int P, int RD, int pad, const SlabPlan &plan, VT *out, hipStream_t st,
                 float *amax_out = nullptr, bool shared_proj = false) {
   // one 1024-thread workgroup per CU (measured best on MI355X: the 47 KB slab is staged once per CU and 16
-  // wavefronts hide the LDS latency); GVL_MSDA_FWD_{THREADS,CHUNKS} override for tuning sweeps
-  const int threads = env_int("GVL_MSDA_FWD_THREADS", 1024);
-  const int nchunk = pick_chunks("GVL_MSDA_FWD_CHUNKS", B * M, Q, 256);
+  // wavefronts hide the LDS latency)
+  const int nchunk = pick_chunks(0, B * M, Q, 256);
   const size_t lds = (size_t)plan.rowsV * 64 * sizeof(float);
   const bool full = L * P == 16;
   decltype(&k_fwd_t1d_d64<kPadZeros, true, FUSED, false, VT>) kern;
@@ -2152,8 +2091,8 @@ int run_fwd_t1d(const VT *value, const int64_t *shapes, const int64_t *lsi, cons
   g_last_impl = FUSED ? 3 : 2;
   g_last_kernel = "k_fwd_t1d_d64";
   return gvl::launch(GVL_PROF_FWD_T1D, Q, B, FUSED ? "k_fwd_t1d_d64<fused>" : "k_fwd_t1d_d64", kern,
-                     dim3(B * M, nchunk), dim3(threads), lds, st, value, shapes, lsi, p0, p1, B, S, M, L, Q, P, RD,
-                     env_int("GVL_MSDA_XCD_PAIRS", 1) ? nchunk : -nchunk, out, g_fwd_stamps,
+                     dim3(B * M, nchunk), dim3(1024), lds, st, value, shapes, lsi, p0, p1, B, S, M, L, Q, P, RD,
+                     nchunk, out, g_fwd_stamps,
                      reinterpret_cast<unsigned *>(amax_out), (Q + nchunk - 1) / nchunk,
                      (M & (M - 1)) == 0 ? __builtin_ctz((unsigned)M) : -1, 1.f / (float)P, shared_proj ? 0 : Q);
 }
@@ -2166,7 +2105,7 @@ int bwd_groups(int B, int M, int nchunk) {
   return g < nchunk ? g : nchunk;
 }
 int bwd_chunks(int B, int M, int Q, int S, int rowsV) {
-  int n = pick_chunks("GVL_MSDA_BWD_CHUNKS", B * M, Q, 256);
+  int n = pick_chunks(env_int("GVL_MSDA_BWD_CHUNKS", 0), B * M, Q, 256);
   while (n <= Q && bwd_lds_bytes(S, (Q + n - 1) / n, rowsV) > kLdsMax) ++n;
   if (n > Q) return 0;
   const int g = bwd_groups(B, M, n);                   // equal shares: a multiple of the group count
@@ -2186,7 +2125,7 @@ bool bwd_split_ok(int B, int S, int M, int L, int P, int Q, const SlabPlan &plan
 // in global memory; -> queries per phase-B chunk, 0 = not eligible
 int bwd_own_chunk(int B, int S, int M, int L, int P, int Q, const SlabPlan &plan, const int64_t *shapes_host) {
   if (!env_int("GVL_MSDA_BWD_OWN", 1)) return 0;
-  if (L != 4 || P != 4 || !plan.ok || !shapes_host || Q < 2 || B * M < env_int("GVL_MSDA_BWD_OWN_MINBM", 64) ||
+  if (L != 4 || P != 4 || !plan.ok || !shapes_host || Q < 2 || B * M < 64 ||
       (B * M >= 256 && (B * M) % 8))
     return 0;
   // WHERE the pair form pays (round 4, T = 100 ... 512, B = 4 ... 64, fused entry points, back to back): it removes the
@@ -2259,7 +2198,7 @@ int run_bwd_t1d(const VT *value, const int64_t *shapes, const int64_t *lsi, cons
     g_last_kernel = "k_bwd_t1d_own";
     return gvl::launch(GVL_PROF_BWD_T1D, Q, B, FUSED ? "k_bwd_t1d_own<fused>" : "k_bwd_t1d_own", kern, dim3(2 * B * M),
                        dim3(kBwdThreads), lds, st, value, shapes, lsi, p0, p1, gout, B, S, M, Q, RD, qc, gvalue, g0, g1,
-                       g_bwd_stamps, env_int("GVL_MSDA_OWN_DEBUG", 0) | ((B * M > 128 && (B * M) % 8 == 0) ? 8 : 0));
+                       g_bwd_stamps, (B * M > 128 && (B * M) % 8 == 0) ? 8 : 0);
   }
   const int ngroup = bwd_groups(B, M, nchunk);
   const size_t lds = bwd_lds_bytes(S, qper, plan.rowsV);

@@ -166,9 +166,6 @@ __device__ __forceinline__ void wgrad_item(const WgParams &p, const int item, co
         const int e = first_live + (int)r;
         r = ((int)r < per_live && e < n_live) ? (uint32_t)p.live[1 + e] : (uint32_t)p.R;
       }
-#ifdef GVL_WG_NO_LOAD
-      s.a[i] = make_float4((float)r, 1.f, 2.f, 3.f); s.b[i] = make_float4(1.f, (float)r, 2.f, 3.f);
-#else
       s.a[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, min(r * a_ld + a_col, kOob), 0, 0));
       if (a_tail < 4) {                              // the piece that straddles column N (N % 4 != 0: the vocabulary layer)
         if (a_tail < 2) s.a[i].y = 0.f;
@@ -176,16 +173,11 @@ __device__ __forceinline__ void wgrad_item(const WgParams &p, const int item, co
         s.a[i].w = 0.f;
       }
       s.b[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, min(r * b_ld + b_col, kOob), 0, 0));
-#endif
     }
   };
   float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);                      // this thread's share of db (tile column 0 only)
   auto store = [&](const Set &s, int buf) {
     unsigned char *st = smem + buf * kWgStageB + st_off;
-#ifdef GVL_WG_NO_STORE
-    for (int i = 0; i < 2; ++i) asm volatile("" ::"v"(s.a[i].x), "v"(s.a[i].w), "v"(s.b[i].x), "v"(s.b[i].w));
-    if (false)
-#endif
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       uint2 hi, lo;
@@ -212,9 +204,6 @@ __device__ __forceinline__ void wgrad_item(const WgParams &p, const int item, co
     return __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) trh4 *)(smem + byte_off));
   };
   auto frag = [&](uint32_t off) {      // 8 consecutive contraction rows of this lane's column
-#ifdef GVL_WG_NO_FRAG
-    return __builtin_bit_cast(h8, make_uint4(off, 1u, 2u, 3u));
-#endif
     const trh4 u = tr(off), v = tr(off + 4 * kWgRowB);
     return __builtin_bit_cast(h8, (__fp16 __attribute__((__vector_size__(16)))){u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]});
   };
@@ -239,12 +228,6 @@ __device__ __forceinline__ void wgrad_item(const WgParams &p, const int item, co
   store(set0, 0);
   load(set0, 3);
   __syncthreads();
-#ifdef GVL_WG_NO_MFMA
-#define GVL_WG_MFMA()                                                                                   \
-  _Pragma("unroll") for (int h = 0; h < 2; ++h) _Pragma("unroll") for (int j = 0; j < 2; ++j) {         \
-    asm volatile("" ::"v"(ah[h]), "v"(al[h]), "v"(bh[h][j]), "v"(bl[h][j]));                            \
-  }
-#else
 #define GVL_WG_MFMA()                                                                                   \
   _Pragma("unroll") for (int h = 0; h < 2; ++h) _Pragma("unroll") for (int j = 0; j < 2; ++j) {         \
     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[h], bh[h][j], acc[j], 0, 0, 0);                  \
@@ -253,7 +236,6 @@ __device__ __forceinline__ void wgrad_item(const WgParams &p, const int item, co
       acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[h], bh[h][j], acc[j], 0, 0, 0);                \
     }                                                                                                   \
   }
-#endif
   // one stage: SET holds the rows of stage S + 1 and is re-requested for stage S + 4 as soon as they are in LDS.  FIRST / SECOND:
   // the two phases in the order of this wavefront's half -- the choice is made ONCE, outside the loop (inside, the accumulators
   // would pass through a phi per stage: hipcc copies all 32 of them twice per stage and every copy waits for the matrix pipe to drain)

@@ -228,11 +228,6 @@ class _Arena:
         return out
 
 
-def _value_flags():
-    """launch flags of the products that write `value` slabs: head m's columns on XCD m (GVL_VALUE_XCD=1; off by default: measured no effect on the sampling launch)"""
-    return LIN_XCD_COLUMNS if os.environ.get("GVL_VALUE_XCD", "0") == "1" else 0
-
-
 def _new(rows, cols, like):
     return torch.empty(rows, cols, device=like.device, dtype=torch.float32)
 
@@ -342,8 +337,7 @@ def encoder_forward(enc, src, temporal_shapes, level_start_index, valid_ratios, 
                                (att.sampling_offsets.weight, att.sampling_offsets.bias),
                                (att.attention_weights.weight, att.attention_weights.bias)])
         value, proj = _new(R, C, x), _new(R, n_proj, x)
-        linear(x, w, [seg(0, value, am_x, rowmask=mask), seg(w.starts[1], proj, am_xp, addend=posf is not None)], a2=posf,
-               flags=_value_flags())
+        linear(x, w, [seg(0, value, am_x, rowmask=mask), seg(w.starts[1], proj, am_xp, addend=posf is not None)], a2=posf)
         o, am_o = _msda(att, value, proj, ref, shapes2d, level_start_index, B, S, arena)
         y = _new(R, C, x)
         linear(o, cached(att, "op", [(att.output_proj.weight, att.output_proj.bias)]), [seg(0, y, am_o, resid=x)])
@@ -445,7 +439,7 @@ class _BoxRefineTrain(torch.autograd.Function):
 def box_refine_train_eligible(delta, ref):
     return (delta.is_cuda and delta.dtype == torch.float32 and ref.dtype == torch.float32 and torch.is_grad_enabled()
             and not torch.is_autocast_enabled() and delta.dim() == 3 and ref.dim() == 3 and ref.shape[-1] in (1, 2)
-            and delta.shape[-1] >= 2 and delta.shape[:2] == ref.shape[:2] and os.environ.get("GVL_BOX_REFINE", "") != "torch")
+            and delta.shape[-1] >= 2 and delta.shape[:2] == ref.shape[:2])
 
 
 def box_refine_train(delta, ref, valid_ratios, want_ref_in):
@@ -554,7 +548,7 @@ class _ClassCountHeads(torch.autograd.Function):
 def class_count_heads_eligible(class_head, hs):
     return (count_pool_train_eligible(hs) and isinstance(class_head, torch.nn.Linear) and class_head.out_features == 1
             and class_head.weight.dtype == torch.float32 and class_head.weight.is_contiguous()
-            and class_head.weight.data_ptr() % 16 == 0 and os.environ.get("GVL_CLASS_COUNT_HEADS", "") != "torch")
+            and class_head.weight.data_ptr() % 16 == 0)
 
 
 def class_count_heads(class_head, hs):
@@ -633,7 +627,7 @@ def embed_rows(weight, ids):
     """weight (V, E)[ids (n)] -> (n, E); training on fp32 CUDA tables: through _EmbedRows"""
     if (weight.is_cuda and weight.dtype == torch.float32 and torch.is_grad_enabled() and weight.requires_grad and weight.dim() == 2
             and weight.is_contiguous() and weight.shape[1] % 4 == 0 and ids.dtype == torch.int64 and ids.dim() == 1
-            and not torch.is_autocast_enabled() and os.environ.get("GVL_EMBED_ROWS", "") != "torch"):
+            and not torch.is_autocast_enabled()):
         return _EmbedRows.apply(weight, ids.contiguous())
     return weight.index_select(0, ids)
 
@@ -676,7 +670,7 @@ def mask_rows(value, padding_mask):
     if (value.is_cuda and value.dtype == torch.float32 and torch.is_grad_enabled() and value.requires_grad and not value.is_leaf
             and value.is_contiguous() and value._base is None and value.dim() == 3 and value.shape[-1] % 4 == 0
             and padding_mask.dtype == torch.bool and padding_mask.shape == value.shape[:2] and value.data_ptr() % 16 == 0
-            and not torch.is_autocast_enabled() and os.environ.get("GVL_MASK_ROWS", "") != "torch"):
+            and not torch.is_autocast_enabled()):
         return _MaskRows.apply(value, padding_mask.contiguous().view(torch.uint8))
     return value.masked_fill(padding_mask[..., None], float(0))
 
@@ -727,8 +721,7 @@ def level_pos_embed_eligible(level_embed, pos_embeds):
     return (level_embed.is_cuda and level_embed.dtype == torch.float32 and torch.is_grad_enabled() and level_embed.requires_grad
             and not torch.is_autocast_enabled() and level_embed.shape[1] % 4 == 0 and 1 <= len(pos_embeds) <= 8
             and level_embed.shape[0] >= len(pos_embeds)
-            and all(p.dtype == torch.float32 and p.dim() == 3 for p in pos_embeds)
-            and os.environ.get("GVL_LEVEL_POS", "") != "torch")
+            and all(p.dtype == torch.float32 and p.dim() == 3 for p in pos_embeds))
 
 
 def level_pos_embed(level_embed, pos_embeds):
@@ -738,7 +731,7 @@ def level_pos_embed(level_embed, pos_embeds):
 def expand_parts_eligible(embed, parts):
     return (embed.is_cuda and embed.dtype == torch.float32 and embed.dim() == 2 and embed.is_contiguous()
             and torch.is_grad_enabled() and embed.requires_grad and not torch.is_autocast_enabled()
-            and embed.shape[1] % (4 * parts) == 0 and os.environ.get("GVL_EXPAND_PARTS", "") != "torch")
+            and embed.shape[1] % (4 * parts) == 0)
 
 
 def expand_parts(embed, B, parts, rows=False):
@@ -750,8 +743,7 @@ def expand_parts(embed, B, parts, rows=False):
 
 def count_pool_train_eligible(hs):
     return (hs.is_cuda and hs.dtype == torch.float32 and hs.dim() == 3 and hs.is_contiguous() and hs.shape[-1] % 4 == 0
-            and torch.is_grad_enabled() and hs.requires_grad and not torch.is_autocast_enabled() and hs.data_ptr() % 16 == 0
-            and os.environ.get("GVL_COUNT_POOL", "") != "torch")
+            and torch.is_grad_enabled() and hs.requires_grad and not torch.is_autocast_enabled() and hs.data_ptr() % 16 == 0)
 
 
 def count_pool_train(hs):
@@ -783,7 +775,7 @@ def _self_attention(layer, x, am_x, am_xp, qpos, B, Q, query_mask, arena):
     H = sa.num_heads
     w = cached(sa, "in", [(sa.in_proj_weight, sa.in_proj_bias)])
     qkv = _new(R, 3 * C, x)
-    own = C == 64 * H and B * H * Q * Q < 2 ** 32 and os.environ.get("GVL_MHA", "") != "torch"
+    own = C == 64 * H and B * H * Q * Q < 2 ** 32
     am_qk, am_v = (arena.take(R), arena.take(R)) if own else (None, None)
     linear(x, w, [seg(0, qkv[:, :2 * C], am_xp, addend=qpos is not None, amax_out=am_qk),
                   seg(2 * C, qkv[:, 2 * C:], am_x, amax_out=am_v)], a2=qpos)
@@ -861,8 +853,7 @@ def _first_layer_constants(dec, layer, rows, query_mask, B, Q):
     rows_key = dec.__dict__.get("_gvl_query_rows_key")
     if rows_key is None:
         return None
-    key = ((rows_key[0], tuple((p_.data_ptr(), p_._version) for p_ in ps if p_ is not None)), B, Q, MSDA.f16_products_now(),
-           os.environ.get("GVL_MHA", ""))
+    key = ((rows_key[0], tuple((p_.data_ptr(), p_._version) for p_ in ps if p_ is not None)), B, Q, MSDA.f16_products_now())
     table = dec.__dict__.setdefault("_gvl_first_layer", {})
     return key, table.get(key)
 
@@ -889,19 +880,17 @@ def decoder_forward(dec, tgt, reference_points, src, src_temporal_shapes, src_le
     arena = _Arena((7 * nl + 2) * (R + 4), tgt.device)          # (+ the row maxima of the q | k and v columns per layer)
     # the first layer's scaled reference points (:302-306) BEFORE the value product: with the first layer's self-attention block kept
     # across forwards (_first_layer_constants) the sampling launch would otherwise directly follow this few-workgroup launch, and a
-    # launch behind one that left most of the chip idle runs 0.5-1 us longer (8.3 against 9.2 us inside the replayed graph, same box,
-    # GVL_REF_FIRST=0; tools/fwd_layer_stamps.py shows the two layers' launches)
-    first_ref_in = None
-    if os.environ.get("GVL_REF_FIRST", "1") != "0":
-        if reference_points.shape[-1] == 2:
-            first_ref_in = reference_points[:, :, None] * torch.stack([src_valid_ratios] * 2, -1)[:, None]
-        else:
-            assert reference_points.shape[-1] == 1
-            first_ref_in = reference_points[:, :, None] * src_valid_ratios[:, None, :, None]
+    # launch behind one that left most of the chip idle runs 0.5-1 us longer (8.3 against 9.2 us inside the replayed graph, same box;
+    # tools/fwd_layer_stamps.py shows the two layers' launches)
+    if reference_points.shape[-1] == 2:
+        first_ref_in = reference_points[:, :, None] * torch.stack([src_valid_ratios] * 2, -1)[:, None]
+    else:
+        assert reference_points.shape[-1] == 1
+        first_ref_in = reference_points[:, :, None] * src_valid_ratios[:, None, :, None]
     # value_proj(memory) of every layer: one product against the concatenated weights
     wv = cached(dec, "values", [(l_.cross_attn.value_proj.weight, l_.cross_attn.value_proj.bias) for l_ in dec.layers])
     values = [_new(Rs, C, mem) for _ in dec.layers]
-    linear(mem, wv, [seg(wv.starts[i], values[i], am_mem, rowmask=mask) for i in range(nl)], flags=_value_flags())
+    linear(mem, wv, [seg(wv.starts[i], values[i], am_mem, rowmask=mask) for i in range(nl)])
     rows = _query_rows(dec, tgt, query_pos, B, Q, C)
     if rows is not None:
         x, qpos, am_x, am_xp = rows
@@ -921,7 +910,7 @@ def decoder_forward(dec, tgt, reference_points, src, src_temporal_shapes, src_le
     for lid, layer in enumerate(dec.layers):
         if next_ref_in is not None:                                               # left by the previous layer's refinement
             ref_in = next_ref_in
-        elif lid == 0 and first_ref_in is not None:
+        elif lid == 0:
             ref_in = first_ref_in
         elif reference_points.shape[-1] == 2:                                     # :302-304
             ref_in = reference_points[:, :, None] * torch.stack([src_valid_ratios] * 2, -1)[:, None]
@@ -952,8 +941,7 @@ def decoder_forward(dec, tgt, reference_points, src, src_temporal_shapes, src_le
                     del table[k_]
                 # (the projection's rows are the same for every video -- same inputs, every output element its own dot product: the
                 #  first video's Q rows are kept and every video reads them, 0.3 instead of 4.9 MB per launch at cfg A)
-                keep_q = os.environ.get("GVL_FIRST_LAYER_SHARED_PROJ", "1") != "0" and B > 1
-                table[first[0]] = (x2, am2, am2p, proj[:Q].clone() if keep_q else proj)
+                table[first[0]] = (x2, am2, am2p, proj[:Q].clone() if B > 1 else proj)
         o, am_o = _msda(att, values[lid], proj, ref_in, shapes2d, src_level_start_index, B, Q, arena)
         y = _new(R, C, x)
         linear(o, cached(att, "op", [(att.output_proj.weight, att.output_proj.bias)]), [seg(0, y, am_o, resid=x2)])

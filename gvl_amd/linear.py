@@ -147,7 +147,7 @@ class _VocabNLLFunction(torch.autograd.Function):
             # dW = g^T x and db = sum_r g in ONE pass over g on the fp16 matrix cores (gvl_wgrad_f16x3_f32): 135 us against the
             # library's 241 us + the column sum's 17 us at (2208, 8518, 512)
             # (the rows of padded positions are zero, and say so in am_g: the product runs over the list of the other rows)
-            gw, gb = MSDA.wgrad(g, x2, am_g, L.row_absmax(x2)[0], skip_zero_rows=os.environ.get("GVL_WGRAD_SKIP", "1") != "0")
+            gw, gb = MSDA.wgrad(g, x2, am_g, L.row_absmax(x2)[0], skip_zero_rows=True)
             return gx, gw, gb, None, None
         gw = g.t().mm(x2) if ctx.needs_input_grad[1] else None
         gb = MSDA.col_sum(g) if ctx.needs_input_grad[2] else None
@@ -251,20 +251,19 @@ class _WgradQueue:
 
 
 _WGRAD_QUEUE = None
-_DEFER_WGRAD = os.environ.get("GVL_WGRAD_GROUP", "") != "0"
 # products over this many rows or more are taken one by one (long videos: the encoder's 15 360 rows at T = 512 -- a launch of its
-# own already fills the chip, and the group's two co-resident workgroups per CU lose to it: tools/switch_sweep.sh)
-_GROUP_MAX_ROWS = int(os.environ.get("GVL_WGRAD_GROUP_MAX_ROWS", "8192"))
+# own already fills the chip, and the group's two co-resident workgroups per CU lose to it)
+_GROUP_MAX_ROWS = 8192
 
 
 class deferred_wgrads:
     """``with deferred_wgrads(): loss.backward()`` -- the layers' weight gradients of this backward pass in grouped launches
-    (see _WgradQueue); flushed on exit.  GVL_WGRAD_GROUP=0: one launch pair per Linear, as in round 5 (A/B switch)."""
+    (see _WgradQueue); flushed on exit.  Outside it, every Linear takes its own launch pair."""
 
     def __enter__(self):
         global _WGRAD_QUEUE
         self.prev = _WGRAD_QUEUE
-        _WGRAD_QUEUE = _WgradQueue() if _DEFER_WGRAD else None
+        _WGRAD_QUEUE = _WgradQueue()
         return self
 
     def __exit__(self, exc_type, exc, tb):

@@ -2,19 +2,14 @@
 ``torch.optim.Adam`` -- on gvl_clip_adam_step_f32 (gvl_optim.hip): three launches over a table of (parameter, gradient, moments)
 instead of torch's ~10 multi-tensor launches that pass over the gradients three times.  The optimizer object, its hyper-parameters
 and its STATE stay torch's (``state_dict`` / checkpoints unchanged): this only replaces what one clip + step computes.
-``GVL_OPTIM=torch`` keeps torch's own launches (A/B switch); anything this path does not cover (several parameter groups, amsgrad,
-maximize, non-fp32 or non-contiguous tensors, state not yet created) falls back to them as well -- same numbers either way, to fp32
-rounding (tests/test_gpu_optim.py)."""
+Anything this path does not cover (several parameter groups, amsgrad, maximize, non-fp32 or non-contiguous tensors, state not yet
+created) falls back to torch's own launches -- same numbers either way, to fp32 rounding (tests/test_gpu_optim.py)."""
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import _lib
-
-_ENABLED = os.environ.get("GVL_OPTIM", "") != "torch"
-
 
 class _Desc(ctypes.Structure):                      # include/gvl_msda.h: gvl_adam_desc
     _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
@@ -83,7 +78,7 @@ class ClipAdam:
     def step(self, params):
         """clip + Adam over `params` (those that have a gradient) -> True, or False when torch's own path must run"""
         g = self._group()
-        if not _ENABLED or g is None or not params or not params[0].is_cuda:
+        if g is None or not params or not params[0].is_cuda:
             return False
         rows = self._state(params)
         if rows is None:

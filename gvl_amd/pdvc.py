@@ -341,8 +341,7 @@ class PDVC(nn.Module):
         dec = self.transformer.decoder.__dict__
         # (training: the decoder leaves the refined boxes of every layer WITH their autograd history; class head and deltas
         #  are shared by the inference path only)
-        take = self.with_box_refine and not disable_refine and (
-            not torch.is_grad_enabled() or os.environ.get("GVL_SHARE_COORDS", "1") != "0")
+        take = self.with_box_refine and not disable_refine
         shared = {k: (dec.get("_gvl_" + k) if take else None) for k in ("cls", "coords", "deltas")}
         same = lambda t_: t_ is not None and t_[l_id].shape[:2] == hs_lid.shape[:2]          # noqa: E731
         if not same(shared["cls"]) and _layers_mod.class_count_heads_eligible(self.class_head[l_id], hs_lid):

@@ -215,8 +215,6 @@ def residual_dropout_norm(x, sub, drop, norm, pos=None, fan=1):
         return y if fan == 1 else (y,) * fan
     from . import layers as L
     assert 1 <= fan <= MAX_FAN
-    if fan > 1 and os.environ.get("GVL_RDLN_FAN", "1") == "0":               # (A/B switch: one handle, autograd adds the gradients)
-        return (residual_dropout_norm(x, sub, drop, norm, pos),) * fan
     *ys, stats = ResidualDropoutLayerNorm.apply(x, sub, norm.weight, norm.bias, norm.eps, p, _site_seed(drop),
                                                 step_counter(x.device) if p > 0 else None, pos, fan)
     for y in ys:

@@ -10,8 +10,7 @@ the attention weights) on the hand-written kernels:
 
 PyTorch runs this as 3 projection GEMMs + 6 elementwise launches + bmm / softmax / dropout / bmm (~250 us forward, ~420 us
 backward per layer at B = 16, Q = 300: profiles/r05_train_timeline_before.txt).  The module keeps its parameters and state-dict
-keys (``in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias``); this file only replaces what its forward launches.
-``GVL_TRAIN_MHA=torch`` keeps nn.MultiheadAttention's own forward (A/B switch)."""
+keys (``in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias``); this file only replaces what its forward launches."""
 import os
 
 import torch
@@ -22,16 +21,6 @@ from . import linear as GL
 from . import train_layers as TL
 from . import MultiScaleDeformableAttention as MSDA
 from .train_planes import Operand
-
-_ENABLED = os.environ.get("GVL_TRAIN_MHA", "") != "torch"
-
-
-def enabled(on=None):
-    global _ENABLED
-    if on is not None:
-        _ENABLED = bool(on)
-    return _ENABLED
-
 
 class _Sub:
     """a K-stage range of operand planes (planes are K-stage-major, so a range of the contraction is a contiguous piece)"""
@@ -205,7 +194,7 @@ class _Core(torch.autograd.Function):
 
 def eligible(mha, tgt, query_pos):
     C = tgt.shape[-1]
-    return (_ENABLED and GL.train_linear_enabled() and isinstance(mha, torch.nn.MultiheadAttention) and mha._qkv_same_embed_dim
+    return (GL.train_linear_enabled() and isinstance(mha, torch.nn.MultiheadAttention) and mha._qkv_same_embed_dim
             and mha.in_proj_bias is not None and mha.bias_k is None and not mha.add_zero_attn and not mha.batch_first
             and tgt.is_cuda and tgt.dtype == torch.float32 and torch.is_grad_enabled() and not torch.is_autocast_enabled()
             and tgt.dim() == 3 and C == mha.embed_dim and C // mha.num_heads == 64 and C % 64 == 0

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the temporal backward at the cfg A decoder / encoder shapes (tools/bwd_phase_stamps.py: per-workgroup phase stamps and
 # dispatch times, back to back), three interleaved rounds.  Two modes:
-#   tools/bwd_ab.sh env NAME=VALUE     the shipped library with and without an environment switch (e.g. GVL_MSDA_BWD_FLAT=0)
+#   tools/bwd_ab.sh env NAME=VALUE     the shipped library with and without an environment switch (e.g. GVL_MSDA_BWD_SPLIT=0)
 #   tools/bwd_ab.sh dev                the shipped library against a timing build in tools/_bin/libgvl_msda_dev.so
 #                                      (made before the call with `python -m gvl_amd.build --dev gvl_msda.hip -D...`)
 # Results under gpurun_out/bwd_ab/.

@@ -1,5 +1,5 @@
-// micro-benchmark (round 5): the training GEMM kernels of gvl_train_gemm.hip as a standalone program (no Python), so that
-// timing-only ablation builds (-DGVL_WG_NO_MFMA ...) of the SAME source can be run side by side in one gpurun call.
+// micro-benchmark (round 5): the training GEMM kernels of gvl_train_gemm.hip as a standalone program (no Python), with the
+// per-phase stamps of a -DGVL_WG_STAMPS build.
 //   usage: tgemm_bench wgrad R N K [iters]
 #include "../../gvl_amd/csrc/gvl_train_gemm.hip"
 
