@@ -19,6 +19,10 @@ _COMMON = dict(
     contrastive_loss_start_coef=0.0, lloss_gau_mask=1, lloss_beta=1,
     enable_contrastive=False, eval_disable_captioning=False, transformer_input_type='queries',
     lr=5e-5, weight_decay=1e-4, grad_clip=100.0, device='cuda',
+    # the trainer's optimizer and learning-rate schedule (train.py:35-54,243-292; gvl_amd.optim.build_optimizer / build_scheduler)
+    optimizer_type='adam', learning_strategy='multi_step', warm_up_ratio=0.1, learning_rate_decay_start=8,
+    learning_rate_decay_every=3, learning_rate_decay_rate=0.5, epoch=30, task_heads_different_lr=False, task_heads_lr=5e-5,
+    only_ft_captioner=False,
 )
 
 CONFIGS = {

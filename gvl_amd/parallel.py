@@ -226,19 +226,29 @@ class TrainStep:
         self.buckets = GradBuckets(self.params, process_group=process_group, flat=flat, overlap=overlap, first=first)
         # fused=True: one multi-tensor kernel per ~100 parameters instead of ~15 foreach kernels each (321 -> ~10
         # launches per step; the step is launch-bound even inside a hipGraph).  Same update rule (train.py:286).
+        # Adam or AdamW, one or two parameter groups, only_ft_captioner: train.py:243-292 (gvl_amd.optim.build_optimizer)
+        from .optim import ClipAdam, build_optimizer
         fused = self.params[0].is_cuda
-        self.optimizer = torch.optim.Adam(self.params, lr=opt.lr, weight_decay=opt.weight_decay,
-                                          capturable=capturable, fused=fused)
+        self.optimizer = build_optimizer(model, opt, self.params, capturable=capturable, fused=fused)
+        self._in_optimizer = {id(p) for g in self.optimizer.param_groups for p in g["params"]}
         # clip + step as three launches over a tensor table (gvl_amd/optim.py); torch's own launches wherever that does not apply
-        from .optim import ClipAdam
         self.clip_adam = ClipAdam(self.optimizer, opt.grad_clip)
         self.world = world_size
 
     def _clip_and_step(self):
         active = [p for p in self.params if p.grad is not None]
-        if not self.clip_adam.step(active):
+        # parameters with a gradient outside the optimizer (only_ft_captioner) are clipped with the rest, not stepped (train.py:407)
+        stepped = [p for p in active if id(p) in self._in_optimizer]
+        clip_only = [p for p in active if id(p) not in self._in_optimizer]
+        if not self.clip_adam.step(stepped, clip_only):
             torch.nn.utils.clip_grad_norm_(active, self.opt.grad_clip)
             self.optimizer.step()
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                # torch's launches took the hyper-parameters as plain numbers: this capture replays them as they are now
+                self._frozen_hyper = self._torch_hyper()
+
+    def _torch_hyper(self):
+        return tuple((g["lr"], g["weight_decay"], tuple(g["betas"]), g["eps"]) for g in self.optimizer.param_groups)
 
     def _forward_loss(self, dt):
         # cache_enabled=False: autocast's weight-cast cache must not live across a hipGraph capture (the cached bf16
@@ -416,8 +426,10 @@ class GraphedTrainStep(TrainStep):
         self.warmup = max(1, int(warmup))
         # Adam creates its state lazily inside the first step(); if that first step were the captured one, the
         # zero-fills of (step, exp_avg, exp_avg_sq) would become graph nodes and every replay would reset the moments.
-        # Create the state now, exactly as torch.optim.Adam._init_group does for capturable=True.
-        for p in self.params:
+        # Create the state now, exactly as torch.optim.Adam._init_group does for capturable=True.  (Only for the optimizer's
+        # parameters: those outside it -- only_ft_captioner -- are clipped, never stepped, and get no state.)
+        self._opt_params = [p for p in self.params if id(p) in self._in_optimizer]
+        for p in self._opt_params:
             st = self.optimizer.state[p]
             if len(st) == 0:
                 st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
@@ -528,7 +540,7 @@ class GraphedTrainStep(TrainStep):
     def _snapshot(self):
         dev = self.params[0].device
         opt_state = [{k: v.clone() for k, v in self.optimizer.state[p].items() if isinstance(v, torch.Tensor)}
-                     for p in self.params]
+                     for p in self._opt_params]
         return ([p.detach().clone() for p in self.params], [b.detach().clone() for b in self.model.buffers()],
                 opt_state, torch.cuda.get_rng_state(dev), torch.get_rng_state())
 
@@ -539,7 +551,7 @@ class GraphedTrainStep(TrainStep):
                 p.copy_(v)                                   # in place: the graphs captured these addresses
             for b, v in zip(self.model.buffers(), buffers):
                 b.copy_(v)
-            for p, saved in zip(self.params, opt_state):
+            for p, saved in zip(self._opt_params, opt_state):
                 for k, v in saved.items():
                     self.optimizer.state[p][k].copy_(v)
         torch.cuda.set_rng_state(cuda_rng, self.params[0].device)
@@ -611,8 +623,23 @@ class GraphedTrainStep(TrainStep):
                 outs = TrainStep.__call__(self, st)
             graphs = (graph,)
         self._restore(snap)
+        # (set by _clip_and_step when the captured update is torch's own: see _check_frozen)
+        graphs[-1].gvl_frozen_hyper = self.__dict__.pop("_frozen_hyper", None)
         self.captures += 1
         return graphs, outs
+
+    def _check_frozen(self, graphs):
+        """the captured update is gvl_clip_adam_groups_step_f32 wherever it applies, and that reads every group's lr, weight decay,
+        betas and eps from device memory (ClipAdam.sync before the replay).  Where torch's own launches were captured instead,
+        they replay the values of the capture: a later change must not be applied silently as a stale value."""
+        frozen = getattr(graphs[-1], "gvl_frozen_hyper", None)
+        if frozen is None:
+            return
+        now = self._torch_hyper()
+        if now != frozen:
+            raise RuntimeError("GraphedTrainStep: this step's update was captured on torch's optimizer launches (an optimizer "
+                               "or tensors gvl_clip_adam_groups_step_f32 does not cover), which keep the hyper-parameters of "
+                               f"the capture {frozen}; they are now {now}")
 
     def _mean_num_boxes_on_device(self, pt):
         """criterion.py:178-181 without a host round trip: load() left this rank's target count in pt.num_boxes; sum over
@@ -664,6 +691,9 @@ class GraphedTrainStep(TrainStep):
                 self.criterion.num_boxes_override = None
             graphs, st, outs = entry
             self._refresh(st, dt)
+        # every group's current lr / weight decay into the update's device table (a copy only when one changed; never a capture)
+        self.clip_adam.sync()
+        self._check_frozen(graphs)
         graphs[0].replay()
         if self.split:
             # eager RCCL between the replays: the first-stage buckets are on the wire while the encoder's backward runs
@@ -685,6 +715,7 @@ class GraphedTrainStep(TrainStep):
         # a replay updates the parameters through the addresses the graph recorded: torch's version counters do not see it, and
         # every weight-derived cache (operand planes, captured eval / decode graphs) is keyed on them
         bump_versions(self.params)
+        self.optimizer._opt_called = True          # (the replay stepped it: torch's LRScheduler checks this flag)
         self.replays += 1
         return outs
 

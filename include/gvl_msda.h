@@ -48,8 +48,10 @@
 extern "C" {
 #endif
 
-#define GVL_MSDA_ABI_VERSION 17
+#define GVL_MSDA_ABI_VERSION 18
 /* ABI history (newest first):
+ * 18: + gvl_clip_adam_groups_step_f32 (clip + Adam / AdamW with each parameter group's hyper-parameters in device memory, so a
+ *      replayed hipGraph follows learning-rate schedules; clip-only tensors); gvl_adam_desc's padding word is now `group`
  * 17: + gvl_msda1d_fused_forward_shared_amax_f32 (one set of offsets / logits rows for every video: the first decoder layer in inference)
  * 16: + gvl_count_pool_f32 / gvl_count_pool_backward_f32 (the count head's pooling over the queries and its gradient, training),
  *      gvl_batch_sum_f32 (the batch-expanded query embedding's gradient), gvl_residual_dropout_layer_norm_backwardn_f32 /
@@ -928,7 +930,7 @@ typedef struct gvl_adam_desc {
   float *m, *v;
   const float *step;
   int64_t n;
-  int vec, pad_;
+  int vec, group; /* group: read by gvl_clip_adam_groups_step_f32 only */
 } gvl_adam_desc;
 int gvl_adam_chunk_elems(void);
 /* writes the gradient addresses (host array of n_tensors device pointers) into the table's `g` fields with a launch whose ARGUMENTS
@@ -939,6 +941,18 @@ int gvl_adam_set_grads(gvl_adam_desc *descs_device, int n_tensors, const void *c
 int gvl_clip_adam_step_f32(const gvl_adam_desc *descs_device, int n_tensors, const int *chunk_map_device, int n_chunks,
                            float *partial_device, float *scal_device, float *corr_device, double max_norm, double lr, double beta1,
                            double beta2, double eps, double weight_decay, void *stream);
+/* the same three launches with the hyper-parameters in DEVICE memory, read when the kernels run: a captured launch keeps its
+ * arguments, so a learning rate passed as one stays the capture's value in every replay; from this table it is whatever the host
+ * wrote before the replay.  hyper: n_groups rows of GVL_ADAM_HYPER_COLS doubles {lr, weight_decay, beta1, beta2, eps, mode, 0, 0};
+ * mode 0 = Adam (weight_decay p added to the clipped gradient), 1 = AdamW (p -= lr weight_decay p before the moment update, as
+ * torch's fused AdamW).  desc.group selects tensor i's row; a group outside [0, n_groups) (-1 by convention) is CLIP-ONLY: its
+ * gradient counts in the total norm and is scaled in place, its parameter is not touched and m, v, step are not read (may be NULL).
+ * corr: {lr_g / (1 - beta1_g^t_i), sqrt(1 - beta2_g^t_i)} per tensor (0, 1 for clip-only ones).  The host checks the values it
+ * writes (lr, eps >= 0, betas in [0, 1)): the launch cannot. */
+#define GVL_ADAM_HYPER_COLS 8
+int gvl_clip_adam_groups_step_f32(const gvl_adam_desc *descs_device, int n_tensors, const int *chunk_map_device, int n_chunks,
+                                  float *partial_device, float *scal_device, float *corr_device, const double *hyper_device,
+                                  int n_groups, double max_norm, void *stream);
 
 #ifdef __cplusplus
 }
