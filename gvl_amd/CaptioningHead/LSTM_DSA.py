@@ -32,6 +32,7 @@ from ..ops.modules import MSDeformAttnCap
 from ..ops.modules.ms_deform_attn import temporal_shapes_2d
 from .. import MultiScaleDeformableAttention as MSDA
 from ..linear import mirror_linear as _mirror_linear, mirror_linear_eligible as _mirror_ok
+from ..graphs import _LRU, capture_on, side_stream
 from ..linear import Linear, split_gemm_enabled, split_linear, vocab_nll, vocab_nll_eligible
 
 
@@ -861,7 +862,9 @@ class Captioner(nn.Module):
     def _decode_graphed(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi):
         """Greedy decoding replayed from a hipGraph: the 31-step loop is ~800 kernel launches whose host-side issue
         cost exceeds their run time; captured once per input shape, replayed with one launch."""
-        cache = self.__dict__.setdefault("_decode_graphs", {})
+        cache = self.__dict__.get("_decode_graphs")
+        if cache is None:
+            cache = self._decode_graphs = _LRU(16)
         # weight-derived operands are cached per parameter version (_inference_weights, _embedding_gates) and become
         # constants of the captured graph: a parameter update must therefore lead to a new capture
         key = (tuple(hs.shape), tuple(reference.shape), tuple(memory.shape), str(hs.device),
@@ -870,18 +873,15 @@ class Captioner(nn.Module):
                sum(p_._version for p_ in self.parameters()))
         if cache and next(iter(cache))[-1] != key[-1]:
             cache.clear()                                    # parameters changed: graphs of the old weights are dead
-        entry = cache.get(key)
+        entry = cache.lookup(key)
         if entry is None:
             static = [t_.clone() for t_ in (hs, reference, memory, mask, valid_ratios)]
-            side = torch.cuda.Stream(device=hs.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                       # warm-up off the capture (lazy inits, LDS attributes)
+            with side_stream(hs.device) as side:                # warm-up off the capture (lazy inits, LDS attributes)
                 self._decode_device(*static, tshapes, lsi, 1, 1.0)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):           # capture on the warm-up stream (see gvl_amd.parallel)
+            with capture_on(side) as graph:
                 outs = self._decode_device(*static, tshapes, lsi, 1, 1.0)
-            entry = cache[key] = (graph, static, outs)
+            entry = (graph, static, outs)
+            cache.store(key, entry)
         graph, static, outs = entry
         for dst, src in zip(static, (hs, reference, memory, mask, valid_ratios)):
             dst.copy_(src)

@@ -13,16 +13,14 @@ module adds what a data-parallel run of the reference loop (train.py:385-409) ne
     mesh (7 links x ~153 GB/s per GPU) large messages are what the ring/direct algorithms need to reach link rate;
   * after backward: wait, scale by 1/world, clip_grad_norm_, Adam step -- train.py:405-409.
 """
-from collections import OrderedDict
-
-import os
-
 import torch
 import torch.distributed as dist
 
+from .graphs import (_Capacity, _Entry, _GraphKey, _LayoutBatch, _LRU, _PaddedBatch, _STATIC_KEYS,  # noqa: F401 (re-exported)
+                     _drop_superseded, _padded_eligible, _shape_sig, capture_on, side_stream)
 from .linear import deferred_wgrads
 from .optim import bump_versions
-from .targets import PaddedTargets, needed_capacity, round_up_pow2, total_events
+from .targets import round_up_pow2
 
 
 def shard_batch(dt, rank, world):
@@ -247,6 +245,18 @@ class TrainStep:
                 # torch's launches took the hyper-parameters as plain numbers: this capture replays them as they are now
                 self._frozen_hyper = self._torch_hyper()
 
+    def _update(self, unused=()):
+        """clip + Adam with `unused` hidden: grad = None while the optimizer looks, as train.py's loop sees parameters
+        that got no gradient -- Adam skips these"""
+        hidden = [(p, p.grad) for p in unused]
+        for p, _ in hidden:
+            p.grad = None
+        try:
+            self._clip_and_step()
+        finally:
+            for p, g in hidden:
+                p.grad = g
+
     def _torch_hyper(self):
         return tuple((g["lr"], g["weight_decay"], tuple(g["betas"]), g["eps"]) for g in self.optimizer.param_groups)
 
@@ -266,12 +276,7 @@ class TrainStep:
         with deferred_wgrads():                                                # (the layers' weight gradients in grouped launches)
             final.backward()
         self.buckets.finish()
-        hidden = [(p, p.grad) for p in self.buckets.unused_params()]
-        for p, _ in hidden:
-            p.grad = None                                   # as train.py's loop sees them: Adam skips these
-        self._clip_and_step()
-        for p, g in hidden:
-            p.grad = g
+        self._update(self.buckets.unused_params())
         return final.detach(), _detached(loss)
 
 
@@ -280,85 +285,6 @@ def _detached(loss):
     whole life -- attached, they hold the step's graph nodes (the parameters' AccumulateGrad nodes among them) alive, and
     the next capture, on another stream, records waits on those nodes' stream into its graph"""
     return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in loss.items()}
-
-
-class _LRU(OrderedDict):
-    """captured graphs, least recently used first; each entry pins a private memory pool, so the cache is bounded"""
-
-    def __init__(self, limit):
-        super().__init__()
-        self.limit = max(1, int(limit))
-
-    def lookup(self, key):
-        entry = self.get(key)
-        if entry is not None:
-            self.move_to_end(key)
-        return entry
-
-    def store(self, key, entry):
-        self[key] = entry
-        self.move_to_end(key)
-        while len(self) > self.limit:
-            self.popitem(last=False)
-
-
-_STATIC_KEYS = ("video_tensor", "video_mask", "video_length")
-
-
-def _drop_superseded(graphs, key, keep_width_buckets=False):
-    """grow-only capacities never shrink, so a padded graph of the same tensor shapes with a smaller one is never
-    replayed again.  Key layout: ("padded", shapes, slots, cap_len, rows[, epoch]); with cap_len_policy="bucket" the
-    caption width is not a grow-only capacity: graphs that differ only in it stay."""
-    def grow_part(k):
-        return ((k[2],) + tuple(k[4:])) if keep_width_buckets else tuple(k[2:])
-    for k in [k for k in graphs if k[0] == "padded" and k[1] == key[1] and grow_part(k) != grow_part(key)]:
-        del graphs[k]
-
-
-class _PaddedBatch:
-    """static device buffers of one captured step: the three feature tensors of pdvc.py:250-258 + PaddedTargets"""
-
-    def __init__(self, dt, slots, cap_len, pair_rows=0):
-        dev = dt["video_tensor"].device
-        self.dt = {k: dt[k].clone() for k in _STATIC_KEYS}
-        self.targets = PaddedTargets(dt["video_tensor"].shape[0], slots, cap_len, dev, pair_rows)
-        self.dt["_gvl_targets"] = self.targets
-        # paths that still want the reference's list (LayerMatch.host(), PostProcess) are served from the host counts
-        self.dt["video_target"] = None
-
-    def load(self, dt, num_boxes=None):
-        for k in _STATIC_KEYS:
-            self.dt[k].copy_(dt[k], non_blocking=True)
-        self.targets.load(dt, num_boxes)
-        for k, v in dt.items():                               # non-tensor bookkeeping travels along (video_key, cap_raw ...)
-            if k not in self.dt and not isinstance(v, torch.Tensor):
-                self.dt[k] = v
-        self.dt["video_target"] = dt["video_target"]
-
-
-class _Capacity:
-    """Grow-only capacities of the padded layout: slots per video = next power of two >= the largest event count seen
-    (>= 4), caption width = next multiple of 4 >= the widest caption tensor seen, caption rows (matched pairs of a
-    whole batch, train only) = next multiple of 32 >= the largest event total seen.  A batch that does not fit raises
-    the capacity and the step is captured again; in a steady run that happens a handful of times, then never."""
-
-    def __init__(self, slots=0, cap_len=0, pair_rows=0, cap_len_policy="grow", cap_len_step=4):
-        self.slots, self.cap_len, self.pair_rows = int(slots or 0), int(cap_len or 0), int(pair_rows or 0)
-        self.cap_len_policy, self.cap_len_step = cap_len_policy, max(1, int(cap_len_step))
-
-    def fit(self, dt, with_captions):
-        n_gt, cap_len = needed_capacity(dt)
-        self.slots = max(self.slots, round_up_pow2(n_gt, 4))
-        if not with_captions:
-            return self.slots, 0
-        step = self.cap_len_step
-        bucket = step * ((max(cap_len, 2) + step - 1) // step)
-        self.cap_len = max(self.cap_len, bucket)
-        self.pair_rows = max(self.pair_rows, 32 * ((max(total_events(dt), 1) + 31) // 32))
-        # "bucket": the step runs at THIS batch's caption-width bucket (one graph per bucket of cap_len_step tokens)
-        # instead of at the widest caption tensor seen so far -- the teacher-forced loop is serial in
-        # the caption length, so a batch of 10-word captions then pays 11 steps, not the 23 a 22-word batch once needed
-        return self.slots, (bucket if self.cap_len_policy == "bucket" else self.cap_len)
 
 
 class GraphedTrainStep(TrainStep):
@@ -421,9 +347,7 @@ class GraphedTrainStep(TrainStep):
                                   32 * ((max_events + 31) // 32) if max_events else 0, cap_len_policy, cap_len_step)
         self.padded = padded
         self.captures = self.replays = 0
-        # >= 1 real step must run before the capture (on a side stream): autograd's gradient accumulators, hipBLASLt
-        # workspaces and the library's lazily built constants have to exist before a stream is capturing
-        self.warmup = max(1, int(warmup))
+        self.warmup = max(1, int(warmup))                    # eager runs before a capture: gvl_amd.graphs.side_stream
         # Adam creates its state lazily inside the first step(); if that first step were the captured one, the
         # zero-fills of (step, exp_avg, exp_avg_sq) would become graph nodes and every replay would reset the moments.
         # Create the state now, exactly as torch.optim.Adam._init_group does for capturable=True.  (Only for the optimizer's
@@ -436,52 +360,21 @@ class GraphedTrainStep(TrainStep):
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
 
-    # ---- batch forms -------------------------------------------------------------------------------------------
-    @staticmethod
-    def _tensor_keys(dt):
-        return [k for k, v in dt.items() if isinstance(v, torch.Tensor)]
-
+    # ---- batch forms (gvl_amd.graphs: _PaddedBatch, _LayoutBatch) -------------------------------------------------
     def _use_padded(self, dt):
         if self.padded is False or self.opt.transformer_input_type != "queries":
             return False
-        slots = max(self.capacity.slots, round_up_pow2(needed_capacity(dt)[0], 4))
-        ok = self.model.supports_padded_targets(self.criterion, eval_mode=False, batch=dt["video_tensor"].shape[0],
-                                                slots=slots)
-        if not ok and self.padded:
-            raise RuntimeError("GraphedTrainStep(padded=True): this model / criterion has no padded-target path")
-        return ok and slots <= min(64, self.opt.num_queries)
+        return _padded_eligible(self.model, self.criterion, self.capacity, dt, eval_mode=False,
+                                num_queries=self.opt.num_queries, required="GraphedTrainStep" if self.padded else None)
 
     def _layout_key(self, dt):
         """fallback form: one graph per batch layout (tensor shapes, events per video, teacher-forcing length)"""
-        sig = tuple((k, tuple(dt[k].shape), str(dt[k].dtype)) for k in self._tensor_keys(dt))
         n_gt = tuple(len(t_["boxes"]) for t_ in dt["video_target"])
         if "_gvl_cap_steps" not in dt:                      # teacher-forcing length: one host read per NEW batch
             live = (dt["cap_tensor"][:, 1:] != 0).any(0).cpu().tolist()
             dt["_gvl_cap_steps"] = min(1 + (live.index(False) if False in live else len(live)),
                                        dt["cap_tensor"].shape[-1] - 1)
-        return "layout", sig, n_gt, dt["_gvl_cap_steps"]
-
-    @staticmethod
-    def _static_copy(dt):
-        st = dict(dt)
-        for k in GraphedTrainStep._tensor_keys(dt):
-            st[k] = dt[k].clone()
-        st["video_target"] = [{k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in t_.items()}
-                              for t_ in dt.get("video_target") or []]
-        return st
-
-    @staticmethod
-    def _refresh(st, dt):
-        for k, v in dt.items():
-            if isinstance(v, torch.Tensor):
-                st[k].copy_(v, non_blocking=True)
-        for a, b in zip(st["video_target"], dt.get("video_target") or []):
-            for k, v in b.items():
-                if isinstance(v, torch.Tensor):
-                    a[k].copy_(v, non_blocking=True)
-
-    def _eager(self, dt):
-        return TrainStep.__call__(self, dt)
+        return _GraphKey("layout", _shape_sig(dt), n_gt, dt["_gvl_cap_steps"])
 
     def _global_num_boxes(self, dt):
         """criterion.py:178-181, outside any capture: mean over the ranks of the (host-known) number of targets, left in
@@ -524,18 +417,6 @@ class GraphedTrainStep(TrainStep):
                 self._cut["src"].backward(self._cut["leaf"].grad)
         self._cut = None
 
-    def _update(self, unused=()):
-        """clip + Adam over the parameters that take part in this captured step; `unused` (found by the warm-up probe)
-        are hidden exactly as TrainStep.__call__ hides them: grad = None while the optimizer looks"""
-        hidden = [(p, p.grad) for p in unused]
-        for p, _ in hidden:
-            p.grad = None
-        try:
-            self._clip_and_step()
-        finally:
-            for p, g in hidden:
-                p.grad = g
-
     # ---- side-effect-free warm-up --------------------------------------------------------------------------------
     def _snapshot(self):
         dev = self.params[0].device
@@ -562,14 +443,11 @@ class GraphedTrainStep(TrainStep):
         captured clip + Adam is agreed ONCE across the ranks from an eager probe step (side-effect free), not per capture --
         GradBuckets.agree_unused.  Until a step where some rank has events, nothing is hidden."""
         snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        with side_stream():
             def fb():
                 self._forward_backward(st)
                 self._backward_encoder()
             unused = self.buckets.probe_unused(fb)
-        torch.cuda.current_stream().wait_stream(side)
         self._restore(snap)
         has_events = sum(len(t_["labels"]) for t_ in dt["video_target"]) > 0
         return self.buckets.agree_unused(unused, has_events)
@@ -585,10 +463,8 @@ class GraphedTrainStep(TrainStep):
         replicas stay identical (the set cannot be agreed inside _capture: captures happen at rank-dependent
         times and must not contain a collective)."""
         snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
         unused = list(hidden) if (hidden and not static_structure) else []     # (agreed across the ranks: _agree_structural)
-        with torch.cuda.stream(side):
+        with side_stream() as side:
             for it in range(self.warmup):
                 if self.split:
                     def fb():
@@ -603,23 +479,17 @@ class GraphedTrainStep(TrainStep):
                     self._update(unused)
                 else:
                     TrainStep.__call__(self, st)
-        torch.cuda.current_stream().wait_stream(side)
-        # capture ON the warm-up stream: autograd's AccumulateGrad nodes were created there and keep running there;
-        # captured from another stream they become a parallel branch of the graph that the optimizer kernels do not
-        # wait for (seen as NaN parameters after a few replays of the bf16 step)
         if self.split:
-            g_fb, g_enc, g_up = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_fb, stream=side):
+            with capture_on(side) as g_fb:
                 outs = self._forward_backward(st)
-            with torch.cuda.graph(g_enc, pool=g_fb.pool(), stream=side):
+            with capture_on(side, g_fb.pool()) as g_enc:
                 self._backward_encoder()
-            with torch.cuda.graph(g_up, pool=g_fb.pool(), stream=side):
+            with capture_on(side, g_fb.pool()) as g_up:
                 self._update(unused)
             self.last_unused = unused
             graphs = (g_fb, g_enc, g_up)
         else:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
+            with capture_on(side) as graph:
                 outs = TrainStep.__call__(self, st)
             graphs = (graph,)
         self._restore(snap)
@@ -656,41 +526,39 @@ class GraphedTrainStep(TrainStep):
         if padded:
             slots, cap_len = self.capacity.fit(dt, with_captions=True)
             rows = min(self.capacity.pair_rows, dt["video_tensor"].shape[0] * min(slots, self.opt.num_queries))
-            key = ("padded", tuple((k, tuple(dt[k].shape), str(dt[k].dtype)) for k in _STATIC_KEYS), slots, cap_len, rows)
-            entry = self.graphs.lookup(key)
-            if entry is None:
-                _drop_superseded(self.graphs, key, self.capacity.cap_len_policy == "bucket")
-                batch = _PaddedBatch(dt, slots, cap_len, rows)
-                batch.load(dt)
-                graphs, outs = self._capture(batch.dt)
-                entry = (graphs, batch, outs)
-                self.graphs.store(key, entry)
-            graphs, batch, outs = entry
-            batch.load(dt)
-            if self.split:
-                self._mean_num_boxes_on_device(batch.targets)       # every rank, every step: one scalar all-reduce
+            key = _GraphKey("padded", _shape_sig(dt, _STATIC_KEYS), slots, cap_len, rows)
         else:
             key = self._layout_key(dt)
-            entry = self.graphs.lookup(key)
-            self.criterion.num_boxes_override = nb              # device scalar read by the captured criterion
+        entry = self.graphs.lookup(key)
+        if padded and entry is None:
+            _drop_superseded(self.graphs, key, self.capacity.cap_len_policy == "bucket")
+            batch = _PaddedBatch(dt, slots, cap_len, rows)
+            batch.load(dt)
+            graphs, outs = self._capture(batch.dt)
+            entry = _Entry(graphs, batch, outs)
+            self.graphs.store(key, entry)
+        elif not padded:
+            self.criterion.num_boxes_override = nb             # device scalar read by the captured criterion
             try:
                 if (self.split and self.world > 1 and self.buckets.flat is not None
                         and self.__dict__.get("_structural") is None):
                     # a collective, so NOT tied to this rank's cache miss: every rank runs it on every layout-keyed step until
                     # the set is agreed (the outcome -- agreed / no rank had events yet -- is the same on all of them)
-                    self._structural = self._agree_structural(GraphedTrainStep._static_copy(dt), dt)
+                    self._structural = self._agree_structural(_LayoutBatch(dt).dt, dt)
                     if self._structural is not None:
                         self.graphs.clear()                      # (captured while nothing was hidden: capture again)
                         entry = None
                 if entry is None:
-                    st = GraphedTrainStep._static_copy(dt)
-                    graphs, outs = self._capture(st, static_structure=False, hidden=self.__dict__.get("_structural"))
-                    entry = (graphs, st, outs)
+                    batch = _LayoutBatch(dt)
+                    graphs, outs = self._capture(batch.dt, static_structure=False, hidden=self.__dict__.get("_structural"))
+                    entry = _Entry(graphs, batch, outs)
                     self.graphs.store(key, entry)
             finally:
                 self.criterion.num_boxes_override = None
-            graphs, st, outs = entry
-            self._refresh(st, dt)
+        graphs, outs = entry.graphs, entry.outs
+        entry.batch.load(dt)
+        if padded and self.split:
+            self._mean_num_boxes_on_device(entry.batch.targets)     # every rank, every step: one scalar all-reduce
         # every group's current lr / weight decay into the update's device table (a copy only when one changed; never a capture)
         self.clip_adam.sync()
         self._check_frozen(graphs)
@@ -771,12 +639,10 @@ class GraphedEvalForward:
         return sum(p_._version for p_ in ps)
 
     def _use_padded(self, dt):
-        if self.padded is False or self.kind != "queries" or self.criterion is None:
+        if self.padded is False or self.kind != "queries":
             return False
-        slots = max(self.capacity.slots, round_up_pow2(needed_capacity(dt)[0], 4))
-        return (self.model.supports_padded_targets(self.criterion, eval_mode=True, batch=dt["video_tensor"].shape[0],
-                                                   slots=slots)
-                and slots <= min(64, self.model.opt.num_queries))
+        return _padded_eligible(self.model, self.criterion, self.capacity, dt, eval_mode=True,
+                                num_queries=self.model.opt.num_queries)
 
     def _autocast(self):
         # inference under autocast follows GVL_AUTOCAST_INFERENCE (gvl_amd/pdvc.py): the fp32-storage path with one ("f16",
@@ -818,7 +684,10 @@ class GraphedEvalForward:
         bounds = list(range(self.decode_chunk + 1, T + 1, self.decode_chunk))
         return bounds + [T + 1]
 
-    def _capture(self, st):
+    def _capture(self, batch):
+        """-> _Entry: graphs = the main graph, then one per further decode segment (same pool); flags[i] = the `alive`
+        flags graphs[i] leaves"""
+        st = batch.dt
         heads = list(self.model.caption_head)
         head = heads[-1]
         bounds = self._segments(head)
@@ -826,102 +695,100 @@ class GraphedEvalForward:
             h_.defer_trim = True
             h_.decode_stop = bounds[0]
         try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
+            with side_stream() as side:
                 for _ in range(self.warmup):
                     self._forward(st)
                     for a, b in zip(bounds[:-1], bounds[1:]):
                         self._continue(head, a, b)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
+            with capture_on(side) as graph:
                 out, loss = self._forward(st)
                 alive0 = getattr(head, "last_alive", None)
             flags = [alive0[:bounds[0] - 1] if alive0 is not None and len(bounds) > 1 else alive0]
-            seg_graphs = []
+            graphs = [graph]
             for a, b in zip(bounds[:-1], bounds[1:]):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=graph.pool(), stream=side):
+                with capture_on(side, graph.pool()) as g:
                     flags.append(self._continue(head, a, b))
-                seg_graphs.append(g)
+                graphs.append(g)
         finally:
             for h_ in heads:
                 h_.defer_trim = False
                 h_.decode_stop = None
                 h_._decode_state = None
         self.captures += 1
-        return graph, seg_graphs, out, loss, flags
+        return _Entry(tuple(graphs), batch, out, loss, flags)
+
+    def _alive_flags(self, entry):
+        """replay the decode segments while captions are still being written -> the `alive` flag of every token booked"""
+        # The forward's only host reads (LSTM_DSA.py:186-187): the `alive` flags of every decode segment that ran.
+        # They are read ONE SEGMENT BEHIND the GPU: segment k + 1 is already queued when the host waits for the flags
+        # of segment k (a stream-ordered copy into pinned memory + an event), so the device never idles on the read;
+        # the price is at most one speculative segment after the last caption has ended -- it only writes columns
+        # that are trimmed below.
+        seg_graphs, flags = entry.graphs[1:], entry.flags
+
+        def post(f_):
+            host = torch.empty(f_.shape, dtype=f_.dtype, pin_memory=True)
+            host.copy_(f_, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            return host, ev
+
+        def take(p_):
+            p_[1].synchronize()
+            return p_[0].tolist()
+        pending = post(flags[0])
+        alive, nxt = [], 0
+        while True:
+            ahead = None
+            if nxt < len(seg_graphs):                       # keep the GPU one segment ahead of the flags in hand
+                seg_graphs[nxt].replay()
+                self.segments_replayed += 1
+                ahead = post(flags[nxt + 1])
+                nxt += 1
+            alive += take(pending)
+            if ahead is None:
+                break
+            if False in alive:                              # every caption ended: the segment in flight is the last one
+                take(ahead)
+                break
+            pending = ahead
+        return alive
 
     @torch.no_grad()
     def __call__(self, dt):
         epoch = self._epoch()
-        if self.graphs and next(iter(self.graphs))[-1] != epoch:
+        if self.graphs and next(iter(self.graphs)).epoch != epoch:
             self.graphs.clear()                              # parameters changed: graphs of the old weights are dead
         padded = self._use_padded(dt)
         if padded:
             slots, _ = self.capacity.fit(dt, with_captions=False)
-            key = ("padded", tuple((k, tuple(dt[k].shape), str(dt[k].dtype)) for k in _STATIC_KEYS), slots, epoch)
+            key = _GraphKey("padded", _shape_sig(dt, _STATIC_KEYS), slots, epoch=epoch)
         else:
-            sig = tuple((k, tuple(v.shape), str(v.dtype)) for k, v in dt.items() if isinstance(v, torch.Tensor))
-            key = ("layout", sig, tuple(len(t_["boxes"]) for t_ in dt.get("video_target") or []), epoch)
+            key = _GraphKey("layout", _shape_sig(dt), tuple(len(t_["boxes"]) for t_ in dt.get("video_target") or []),
+                            epoch=epoch)
         entry = self.graphs.lookup(key)
         if entry is None:
             if padded:
                 _drop_superseded(self.graphs, key)
                 batch = _PaddedBatch(dt, slots, 0)
                 batch.load(dt)
-                st = batch.dt
             else:
-                batch, st = None, GraphedTrainStep._static_copy(dt)
-            entry = (batch, st) + self._capture(st)
+                batch = _LayoutBatch(dt)
+            entry = self._capture(batch)
             self.graphs.store(key, entry)
-        batch, st, graph, seg_graphs, out, loss, flags = entry
-        if batch is not None:
-            batch.load(dt)
-        else:
-            GraphedTrainStep._refresh(st, dt)
-        graph.replay()
+        entry.batch.load(dt)
+        entry.graphs[0].replay()
         self.replays += 1
-        out = dict(out)
+        out = dict(entry.outs)
         for m in self._matches(out):
             m.invalidate()                                   # the device indices changed under the cached host copy
-        if flags[0] is not None and isinstance(out.get("seq"), torch.Tensor) and not self.model.opt.eval_disable_captioning:
-            # The forward's only host reads (LSTM_DSA.py:186-187): the `alive` flags of every decode segment that ran.
-            # They are read ONE SEGMENT BEHIND the GPU: segment k + 1 is already queued when the host waits for the flags
-            # of segment k (a stream-ordered copy into pinned memory + an event), so the device never idles on the read;
-            # the price is at most one speculative segment after the last caption has ended -- it only writes columns
-            # that are trimmed below.
-            def post(f_):
-                host = torch.empty(f_.shape, dtype=f_.dtype, pin_memory=True)
-                host.copy_(f_, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                return host, ev
-
-            def take(p_):
-                p_[1].synchronize()
-                return p_[0].tolist()
-            pending = post(flags[0])
-            alive, nxt = [], 0
-            while True:
-                ahead = None
-                if nxt < len(seg_graphs):                       # keep the GPU one segment ahead of the flags in hand
-                    seg_graphs[nxt].replay()
-                    self.segments_replayed += 1
-                    ahead = post(flags[nxt + 1])
-                    nxt += 1
-                alive += take(pending)
-                if ahead is None:
-                    break
-                if False in alive:                              # every caption ended: the segment in flight is the last one
-                    take(ahead)
-                    break
-                pending = ahead
+        if (entry.flags[0] is not None and isinstance(out.get("seq"), torch.Tensor)
+                and not self.model.opt.eval_disable_captioning):
+            alive = self._alive_flags(entry)
             keep = alive.index(False) if False in alive else len(alive)
             if keep == 0:
                 out["seq"], out["caption_probs"] = [], {"cap_prob_eval": []}
             else:
                 out["seq"] = out["seq"][..., :keep]
                 out["caption_probs"] = {"cap_prob_eval": out["caption_probs"]["cap_prob_eval"][..., :keep]}
-        return out, loss
+        return out, entry.loss

@@ -75,6 +75,33 @@ def test_capacity_policies_and_graph_cache():
     assert ("padded", sig, 8, 8, 32) not in graphs
 
 
+def test_layout_batch_refreshes_in_place_and_carries_bookkeeping():
+    """the fallback batch form of a captured step: load() copies every tensor (those of video_target too) into the addresses
+    the graph recorded and takes the non-tensor entries of the new batch"""
+    from gvl_amd.graphs import _LayoutBatch
+    dt = synth_batch(2, 6, 8, 30, [2, 3], "cpu", seed=1, cap_words=3)
+    dt2 = synth_batch(2, 6, 8, 30, [2, 3], "cpu", seed=2, cap_words=3)
+    dt["video_key"], dt2["video_key"] = ["a", "b"], ["c", "d"]
+    batch = _LayoutBatch(dt)
+
+    def tensors(d):
+        flat = {k: v for k, v in d.items() if isinstance(v, torch.Tensor)}
+        for i, t_ in enumerate(d["video_target"]):
+            flat.update({(i, k): v for k, v in t_.items() if isinstance(v, torch.Tensor)})
+        return flat
+    before = {k: v.data_ptr() for k, v in tensors(batch.dt).items()}
+    assert before and not set(before.values()) & {v.data_ptr() for v in tensors(dt).values()}      # copies, not aliases
+    batch.load(dt2)
+    now, want = tensors(batch.dt), tensors(dt2)
+    assert set(now) == set(want) == set(before)
+    for k, v in now.items():
+        assert torch.equal(v, want[k]) and v.data_ptr() == before[k], k
+    for k, v in dt2.items():
+        if not isinstance(v, torch.Tensor) and k != "video_target":
+            assert batch.dt[k] is v, k
+    assert batch.dt["video_key"] == ["c", "d"]
+
+
 def test_graph_replay_guard_detects_a_late_environment_setting():
     """DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 must be in place before the HIP runtime initialises; gvl_amd records when it
     was not and the captured steps refuse to capture (a fresh interpreter per case: the flag is computed at import)"""
