@@ -851,6 +851,78 @@ class Captioner(nn.Module):
                 else:
                     st["logits"] = self.logit(self.dropout(getattr(out, "_gvl_lowp", out)))
 
+    def _beam_device(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi, beam_size, length_penalty):
+        """The whole beam search on the device, no host interaction -> (tokens (n, W, T), logprobs
+        (n, W, T), scores (n, W), lengths (n, W), alive (T,)) in final rank order, T = max_caption_len.  Capturable in a hipGraph.
+        The W beams of an event are W consecutive query rows: hs, the reference points and every per-query constant of
+        core.prepare are the same inside such a group, so the token step (core.step, unchanged) runs on n W rows and only h and
+        c are re-ordered by parent beam -- by the kernel that selects the beams (gvl_beam_step_f32), one launch per token."""
+        W, T, H, V1 = beam_size, self.max_caption_len, self.rnn_size, self.vocab_size + 1
+        n = hs.shape[0] * hs.shape[1]
+        R = n * W
+        dev = hs.device
+        hs = hs.repeat_interleave(W, 1)
+        ref_in = self._scaled_reference(reference.repeat_interleave(W, 1), {'valid_ratios': valid_ratios})
+        const = self.core.prepare(hs, memory, mask)
+        emb_gates = self._embedding_gates(const.get("gate_perm"))
+        # one zero fill: h = c = 0, the <bos> ids, the first step's finished flags and the per-step `alive` words
+        n_f = 2 * R * H
+        b_l = (8 * R + 15) // 16 * 16
+        raw = torch.zeros(4 * n_f + b_l + 4 * T + R, dtype=torch.uint8, device=dev)
+        h = raw[:4 * R * H].view(torch.float32).view(R, H)
+        c = raw[4 * R * H:4 * n_f].view(torch.float32).view(R, H)
+        it = raw[4 * n_f:4 * n_f + 8 * R].view(torch.long)
+        alive = raw[4 * n_f + b_l:4 * n_f + b_l + 4 * T].view(torch.int32)
+        fin = raw[4 * n_f + b_l + 4 * T:].view(n, W)
+        score = torch.full((n, W), float("-inf"), dtype=torch.float32, device=dev)
+        score[:, 0] = 0.0                                              # beam 0 alone is live: the first step yields W distinct beams
+        scores = (torch.empty_like(score), torch.empty_like(score))
+        fins = (torch.empty_like(fin), torch.empty_like(fin))
+        states = ((torch.empty_like(h), torch.empty_like(c)), (torch.empty_like(h), torch.empty_like(c)))
+        parents = torch.empty(T, n, W, dtype=torch.int32, device=dev)
+        tokens = torch.empty(T, n, W, dtype=torch.long, device=dev)
+        logps = torch.empty(T, n, W, dtype=torch.float32, device=dev)
+        ld = (V1 + 3) // 4 * 4                                          # rows of the logits padded to 16 bytes
+        logit_buf = torch.empty(R, ld, dtype=torch.float32, device=dev)
+        for t in range(T):
+            out, (h, c) = self.core.step((emb_gates, it), (h, c), hs, ref_in, tshapes, lsi, const)
+            planes = self._logit_planes(out)
+            if planes is not None:                                      # fp32 product on the fp16 matrix cores
+                hp = getattr(out, "_gvl_planes", None)
+                logits = MSDA.gemm_f16x3(hp if hp is not None else MSDA.split_rows(out), planes, self.logit.bias,
+                                         out=logit_buf[:, :V1])
+            else:
+                logits = self.logit(self.dropout(out)).float().contiguous()
+            MSDA.beam_step(logits, score, fin, h, c, scores[t & 1], fins[t & 1], parents[t], tokens[t], logps[t],
+                           alive[t:t + 1], *states[t & 1])
+            score, fin, (h, c), it = scores[t & 1], fins[t & 1], states[t & 1], tokens[t].view(-1)
+        return MSDA.beam_finish(parents, tokens, logps, score, length_penalty) + (alive.view(T) != 0,)
+
+    def beam_search(self, hs, reference, others, beam_size, length_penalty=0.0):
+        """Beam-search decoding (the `beam_size` option the reference reads at LSTM_DSA.py:132 and drops; semantics: DESIGN.md
+        section 4.3) -> dict, every entry in final rank order (rank = score / len ** length_penalty, len = emitted tokens with
+        the end token; the penalty is never applied during the search):
+            tokens (n, W, T) int64 and logprobs (n, W, T), zero behind a beam's end token;  scores (n, W) sum of log-probs;
+            lengths (n, W) tokens in front of the end token;  alive (T,) bool: some beam is still live after token t.
+        No host read in here.  With graph_decode set the loop is replayed from a hipGraph: the outputs are then the graph's static
+        tensors, overwritten by the next call."""
+        W = int(beam_size)
+        if not 1 <= W <= MSDA.BEAM_MAX:
+            raise ValueError(f"beam_size must be 1 .. {MSDA.BEAM_MAX} (got {beam_size})")
+        if W > self.vocab_size + 1:
+            raise ValueError(f"beam_size {W} exceeds the {self.vocab_size + 1} vocabulary entries")
+        if torch.is_autocast_enabled():
+            raise NotImplementedError("beam search decodes in fp32: the bf16-storage decode under torch.autocast is not built")
+        if torch.is_grad_enabled():
+            raise RuntimeError("beam search is inference only: call it under torch.no_grad()")
+        memory, tshapes, lsi, mask, _ = self._level_inputs(others, reference)
+        args = (hs, reference, memory, mask, others['valid_ratios'], tshapes, lsi)
+        if getattr(self, "graph_decode", False) and getattr(tshapes, "_gvl_host_lengths", None) is not None:
+            out = self._decode_graphed(*args, beam=(W, float(length_penalty)))
+        else:
+            out = self._beam_device(*args, W, float(length_penalty))
+        return dict(zip(("tokens", "logprobs", "scores", "lengths", "alive"), out))
+
     def decode_continue(self, t0, t1):
         """continue a greedy loop that `decode_stop` cut at iteration t0 (gvl_amd.parallel.GraphedEvalForward captures
         the loop in segments and stops replaying them once every caption has ended) -> alive flags of the tokens this
@@ -859,9 +931,10 @@ class Captioner(nn.Module):
         self._greedy_iterations(st, t0, t1)
         return st["alive"][t0 - 1:t1 - 1].view(torch.bool)
 
-    def _decode_graphed(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi):
+    def _decode_graphed(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi, beam=(1, 0.0)):
         """Greedy decoding replayed from a hipGraph: the 31-step loop is ~800 kernel launches whose host-side issue
-        cost exceeds their run time; captured once per input shape, replayed with one launch."""
+        cost exceeds their run time; captured once per input shape, replayed with one launch.
+        beam = (beam_size, length_penalty) with beam_size > 1: the beam search (_beam_device) instead, by the same cache."""
         cache = self.__dict__.get("_decode_graphs")
         if cache is None:
             cache = self._decode_graphs = _LRU(16)
@@ -869,17 +942,21 @@ class Captioner(nn.Module):
         # constants of the captured graph: a parameter update must therefore lead to a new capture
         key = (tuple(hs.shape), tuple(reference.shape), tuple(memory.shape), str(hs.device),
                tuple(tshapes._gvl_host_lengths[0]),
-               torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else None,
+               torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else None, tuple(beam),
                sum(p_._version for p_ in self.parameters()))
         if cache and next(iter(cache))[-1] != key[-1]:
             cache.clear()                                    # parameters changed: graphs of the old weights are dead
         entry = cache.lookup(key)
         if entry is None:
             static = [t_.clone() for t_ in (hs, reference, memory, mask, valid_ratios)]
+            if beam[0] > 1:
+                decode = lambda: self._beam_device(*static, tshapes, lsi, *beam)      # noqa: E731
+            else:
+                decode = lambda: self._decode_device(*static, tshapes, lsi, 1, 1.0)   # noqa: E731
             with side_stream(hs.device) as side:                # warm-up off the capture (lazy inits, LDS attributes)
-                self._decode_device(*static, tshapes, lsi, 1, 1.0)
+                decode()
             with capture_on(side) as graph:
-                outs = self._decode_device(*static, tshapes, lsi, 1, 1.0)
+                outs = decode()
             entry = (graph, static, outs)
             cache.store(key, entry)
         graph, static, outs = entry
@@ -890,9 +967,23 @@ class Captioner(nn.Module):
 
     @_bf16_decode
     def sample(self, hs, reference, others, opt={}):
-        """Greedy / multinomial decoding (LSTM_DSA.py:126-194) -> (seq (B*Q, <=max_len), logprobs)."""
+        """Greedy / multinomial decoding (LSTM_DSA.py:126-194) -> (seq (B*Q, <=max_len), logprobs).
+        opt['beam_size'] > 1 (with opt['length_penalty'], default 0): the best beam of beam_search in the same form."""
         sample_max = opt.get('sample_max', 1)
         temperature = opt.get('temperature', 1.0)
+        beam_size = int(opt.get('beam_size', 1) or 1)
+        if beam_size > 1:
+            # the best beam in the greedy branch's form: (n, keep) with keep = the longest returned caption, ([], []) when
+            # every one is empty -- PostProcess reads it as it reads greedy output
+            if not sample_max:
+                raise ValueError("beam_size > 1 needs sample_max = 1: beam search and multinomial sampling exclude each other")
+            if getattr(self, "defer_trim", False):
+                raise NotImplementedError("beam search inside a captured whole forward (defer_trim) is not built")
+            res = self.beam_search(hs, reference, others, beam_size, opt.get('length_penalty', 0.0))
+            keep = int(res["lengths"][:, 0].max())                   # the one host read
+            if keep == 0:
+                return [], []
+            return res["tokens"][:, 0, :keep].clone(), res["logprobs"][:, 0, :keep].clone()
         memory, tshapes, lsi, mask, _ = self._level_inputs(others, reference)
         if getattr(self, "defer_trim", False):
             # caller is capturing the whole forward in a hipGraph (gvl_amd.parallel.GraphedEvalForward): no host read

@@ -850,11 +850,73 @@ def greedy_step_and_gemm(logits, t_col, unfinished, seq, seq_lp, alive, a, b, bi
     return tok, out
 
 
+BEAM_MAX = 8          # include/gvl_msda.h: gvl_beam_step_f32 serves 1 <= W <= 8
+
+
+def beam_step(logits, score_in, fin_in, h_in, c_in, score_out, fin_out, parent, token, logp, alive, h_out, c_out):
+    """one token of the beam search (include/gvl_msda.h: gvl_beam_step_f32): logits (n W, V) fp32 with unit column stride (the
+    row stride may be padded), score_in / fin_in (n, W) fp32 / uint8, h_in / c_in (n W, H) the state rows the step left.  Writes
+    the W best continuations of every event row in descending order of score -- score_out, fin_out, parent (int32), token
+    (int64: also the next step's input ids), logp, all (n, W) -- the rows of h_in / c_in re-ordered by parent into h_out / c_out,
+    and ORs 1 into alive (one int32, zero-initialised) when a beam is still live after the step."""
+    _require(score_in.dim() == 2, "beam_step: score_in must be (n, W)")
+    n, W = score_in.shape
+    _require(1 <= W <= BEAM_MAX, f"beam_step: beam width must be 1 .. {BEAM_MAX} (got {W})")
+    _require(logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == n * W
+             and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1] and logits.shape[1] >= W,
+             "beam_step: logits must be an (n W, V >= W) fp32 CUDA matrix with unit column stride")
+    V = logits.shape[1]
+    _require(h_in.dim() == 2 and h_in.shape[0] == n * W and h_in.shape[1] % 4 == 0, "beam_step: h_in must be (n W, H), H % 4 == 0")
+    H = h_in.shape[1]
+    for name, t_, dt, shape in (("score_in", score_in, torch.float32, (n, W)), ("fin_in", fin_in, torch.uint8, (n, W)),
+                                ("score_out", score_out, torch.float32, (n, W)), ("fin_out", fin_out, torch.uint8, (n, W)),
+                                ("parent", parent, torch.int32, (n, W)), ("token", token, torch.int64, (n, W)),
+                                ("logp", logp, torch.float32, (n, W)), ("alive", alive, torch.int32, (1,)),
+                                ("h_in", h_in, torch.float32, (n * W, H)), ("c_in", c_in, torch.float32, (n * W, H)),
+                                ("h_out", h_out, torch.float32, (n * W, H)), ("c_out", c_out, torch.float32, (n * W, H))):
+        _require(t_.device == logits.device and t_.dtype == dt and tuple(t_.shape) == shape and t_.is_contiguous(),
+                 f"beam_step: {name} must be a contiguous {dt} tensor of shape {shape} on the logits' device")
+    for name, a, b in (("h", h_in, h_out), ("c", c_in, c_out), ("score", score_in, score_out), ("fin", fin_in, fin_out)):
+        _require(a.data_ptr() != b.data_ptr(), f"beam_step: {name}_in and {name}_out ping-pong, nothing is updated in place")
+    _require(all(t_.data_ptr() % 16 == 0 for t_ in (h_in, c_in, h_out, c_out)), "beam_step: the state buffers must be 16-byte aligned")
+    with torch.cuda.device(logits.device):
+        rc = _lib.lib().gvl_beam_step_f32(logits.data_ptr(), logits.stride(0), n, W, V, score_in.data_ptr(), fin_in.data_ptr(),
+                                          h_in.data_ptr(), c_in.data_ptr(), H, score_out.data_ptr(), fin_out.data_ptr(),
+                                          parent.data_ptr(), token.data_ptr(), logp.data_ptr(), alive.data_ptr(),
+                                          h_out.data_ptr(), c_out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "beam_step")
+
+
+def beam_finish(parents, tokens, logps, score, length_penalty=0.0):
+    """final ranking and back-trace of a beam search (include/gvl_msda.h: gvl_beam_finish_f32): parents (T, n, W) int32, tokens
+    (T, n, W) int64 and logps (T, n, W) as beam_step recorded them, score (n, W) of the last step -> in rank order (score /
+    len ** length_penalty, ties to the smaller beam) tokens (n, W, T) int64, logprobs (n, W, T), scores (n, W) and lengths (n, W)
+    int64 (tokens in front of the end token)"""
+    _require(parents.dim() == 3, "beam_finish: parents must be (T, n, W)")
+    T, n, W = parents.shape
+    _require(1 <= W <= BEAM_MAX and T >= 1, f"beam_finish: needs 1 <= W <= {BEAM_MAX} and T >= 1")
+    for name, t_, dt, shape in (("parents", parents, torch.int32, (T, n, W)), ("tokens", tokens, torch.int64, (T, n, W)),
+                                ("logps", logps, torch.float32, (T, n, W)), ("score", score, torch.float32, (n, W))):
+        _require(t_.is_cuda and t_.device == parents.device and t_.dtype == dt and tuple(t_.shape) == shape and t_.is_contiguous(),
+                 f"beam_finish: {name} must be a contiguous {dt} CUDA tensor of shape {shape}")
+    dev = parents.device
+    out_t = torch.empty(n, W, T, dtype=torch.int64, device=dev)
+    out_lp = torch.empty(n, W, T, dtype=torch.float32, device=dev)
+    out_s = torch.empty(n, W, dtype=torch.float32, device=dev)
+    out_len = torch.empty(n, W, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gvl_beam_finish_f32(parents.data_ptr(), tokens.data_ptr(), logps.data_ptr(), score.data_ptr(), n, W, T,
+                                            float(length_penalty), out_t.data_ptr(), out_lp.data_ptr(), out_s.data_ptr(),
+                                            out_len.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "beam_finish")
+    return out_t, out_lp, out_s, out_len
+
+
 PROF_TAGS = {1: "fwd_t1d_d64", 2: "fwd_generic", 3: "bwd_t1d_d64", 4: "bwd_generic", 5: "sample", 6: "sum_partials",
              7: "sample_bwd", 8: "cap_attend", 9: "row_argmax_lse", 10: "lstm_cell", 11: "lsap",
              12: "cap_train_fwd", 13: "cap_train_bwd", 14: "lstm_train", 15: "match_cost", 16: "criterion",
              17: "pos_embed", 18: "col_sum", 19: "proj", 20: "split_rows", 21: "gemm_f16x3", 22: "layer_gemm",
-             23: "layer_norm_etc", 24: "wgrad_f16x3", 25: "mha_train"}
+             23: "layer_norm_etc", 24: "wgrad_f16x3", 25: "mha_train", 26: "beam_step", 27: "beam_finish"}
 
 
 def clock_probe_mhz(device=None, n_fma=20000):

@@ -11,6 +11,7 @@ _COMMON = dict(
     transformer_ff_dim=512, transformer_dropout_prob=0.1, with_box_refine=1, aux_loss=True, num_classes=1,
     max_eseq_length=10, share_caption_head=1, disable_mid_caption_heads=False,
     caption_decoder_type='standard', cap_nheads=1, cap_dec_n_points=4, cap_num_feature_levels=4, max_caption_len=30,
+    beam_size=1, beam_length_penalty=0.0,
     att_hid_size=512, rnn_size=512, input_encoding_size=512, num_layers=1, drop_prob=0.5, clip_context_dim=512,
     wordRNN_input_feats_type='C', enable_pos_emb_for_captioner=False,
     set_cost_class=2, set_cost_bbox=0, set_cost_giou=4, set_cost_cl=2.0, cost_alpha=0.25, cost_gamma=2,

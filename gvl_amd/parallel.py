@@ -756,6 +756,9 @@ class GraphedEvalForward:
 
     @torch.no_grad()
     def __call__(self, dt):
+        if int(vars(self.model.opt).get('beam_size', 1) or 1) > 1:
+            raise NotImplementedError("GraphedEvalForward captures the greedy decoding loop in segments; beam search (opt.beam_size "
+                                      "> 1) is not served here: run the eager forward, or set graph_decode on the caption head")
         epoch = self._epoch()
         if self.graphs and next(iter(self.graphs)).epoch != epoch:
             self.graphs.clear()                              # parameters changed: graphs of the old weights are dead

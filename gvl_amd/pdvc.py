@@ -473,7 +473,10 @@ class PDVC(nn.Module):
         if decoder_type != 'standard':
             raise ValueError(f"caption_decoder_type {decoder_type!r} is not built by gvl_amd")
         with torch.no_grad():
-            seq, cap_prob_eval = cap_head.sample(hs, reference, others)
+            # beam_size: read AND honoured (the reference reads it at LSTM_DSA.py:132 and decodes greedily); 1 = the greedy path
+            seq, cap_prob_eval = cap_head.sample(hs, reference, others,
+                                                 {'beam_size': vars(self.opt).get('beam_size', 1),
+                                                  'length_penalty': vars(self.opt).get('beam_length_penalty', 0.0)})
             if len(seq):
                 seq = seq.reshape(-1, N_q, seq.shape[-1])
                 cap_prob_eval = cap_prob_eval.reshape(-1, N_q, cap_prob_eval.shape[-1])

@@ -48,8 +48,11 @@
 extern "C" {
 #endif
 
-#define GVL_MSDA_ABI_VERSION 18
+#define GVL_MSDA_ABI_VERSION 19
 /* ABI history (newest first):
+ * 19: + gvl_beam_step_f32 / gvl_beam_finish_f32 (beam-search decoding of the captioner: per token the top W of W * V continuation
+ *      scores with finished-beam handling and the re-ordering of the recurrent state by parent beam in one launch; the final
+ *      ranking and back-trace); profiling tags GVL_PROF_BEAM / GVL_PROF_BEAM_FINISH
  * 18: + gvl_clip_adam_groups_step_f32 (clip + Adam / AdamW with each parameter group's hyper-parameters in device memory, so a
  *      replayed hipGraph follows learning-rate schedules; clip-only tensors); gvl_adam_desc's padding word is now `group`
  * 17: + gvl_msda1d_fused_forward_shared_amax_f32 (one set of offsets / logits rows for every video: the first decoder layer in inference)
@@ -538,6 +541,8 @@ int gvl_ce_rows_backward_f32(float *logits, int64_t ld, int R, int V, const int6
 #define GVL_PROF_LAYER_NORM 23
 #define GVL_PROF_WGRAD 24
 #define GVL_PROF_MHA_TRAIN 25
+#define GVL_PROF_BEAM 26
+#define GVL_PROF_BEAM_FINISH 27
 int gvl_prof_enable(int on);   /* 0 off | 1 sampling-path kernels | 2 also GVL_PROF_PROJ (stamping two consecutive launches
                                   inflates the second one's interval by 2-3 us, so level 1 leaves the projection alone) */
 /* Phase stamps of the temporal kernels (diagnostics): while a DEVICE buffer of 2 x 4096 x 4 uint64 is set, every
@@ -745,6 +750,32 @@ int gvl_row_argmax_lse_f32(const float *logits, int R, int V, int64_t *idx, floa
  *    reference feeds to the next LSTM step). */
 int gvl_greedy_step_f32(const float *logits, int R, int V, int first_step, int64_t *token, float *logp,
                         unsigned char *unfinished, int64_t *seq_col, float *seq_lp_col, int seq_ld, void *stream);
+
+/* -- BEAM SEARCH (ABI 19; gvl_beam.hip).  Replaces nothing the reference computes: its Captioner.sample reads
+ *    opt.get('beam_size', 1) (LSTM_DSA.py:132, LSTM.py:106) and drops it, so a caller asking for beam_size = 3 gets greedy captions.
+ *    This is that option, with the semantics of DESIGN.md section 4.3; in ATen a token would be a chain of log_softmax / topk /
+ *    gather / index_select launches.
+ *    gvl_beam_step_f32: one token of the search for n event rows of W beams (1 <= W <= 8, W <= V), one workgroup per event row.
+ *      logits    (n W, V) fp32, row stride logits_ld >= V elements (a stride that is a multiple of 4 keeps the rows 16-byte aligned)
+ *      score_in  (n, W) sum of log-probs per beam (first step: 0, -inf, ...); fin_in (n, W) bytes, non-zero = has emitted <end> = 0
+ *      h_in, c_in (n W, H) fp32 state rows the step left, H % 4 == 0, 16-byte aligned
+ *    A live beam b offers (b, v) at score_in[b] + log_softmax(logits[b])[v] for every v, a finished one (b, 0) at score_in[b] with a
+ *    token log-prob of 0.  The W best become the new beams in descending order of score, equal scores by the smaller b V + v:
+ *      score_out, fin_out (n, W): fin_out = fin_in[parent] | (token == 0);   parent_out (n, W) int;   logp_out (n, W)
+ *      token_out (n, W) int64: the step's record AND the next step's input ids (a finished beam is fed 0; its state is never read again)
+ *      *alive |= 1 when some beam of some row is still live after the step (int, zeroed by the caller: an integer atomic OR)
+ *      h_out, c_out (n W, H): row (r, j) = h_in / c_in row (r, parent[r, j]).  Every *_out is another buffer than its *_in.
+ *    gvl_beam_finish_f32: final ranking and back-trace of T recorded steps.  parents (T, n, W) int, tokens (T, n, W) int64, logps
+ *      (T, n, W), score (n, W) of the last step.  rank value = score / len^length_penalty, len = emitted tokens with the end token
+ *      (1 .. T); ties to the smaller beam.  In rank order: out_tokens / out_logps (n, W, T) (zero behind the end token), out_scores
+ *      (n, W) the plain sums of log-probs, out_lengths (n, W) int64 = tokens in front of the end token. */
+int gvl_beam_step_f32(const float *logits, int64_t logits_ld, int n, int W, int V, const float *score_in,
+                      const unsigned char *fin_in, const float *h_in, const float *c_in, int H, float *score_out,
+                      unsigned char *fin_out, int *parent_out, int64_t *token_out, float *logp_out, int *alive,
+                      float *h_out, float *c_out, void *stream);
+int gvl_beam_finish_f32(const int *parents, const int64_t *tokens, const float *logps, const float *score, int n, int W, int T,
+                        float length_penalty, int64_t *out_tokens, float *out_logps, float *out_scores, int64_t *out_lengths,
+                        void *stream);
 
 /* -- bf16-input twins of the three inference token-step kernels (BASELINE config 4, "CaptioningHead cross-attn, bf16"):
  *    under torch.autocast the GEMMs of the token loop leave the slab, h2att(h), the gate pre-activations, the
