@@ -6,7 +6,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GVL_LIB_PATH: a dev build (gvl_amd.build.build_dev: timing / ablation variants of single kernels) instead of the shipped library
 LIB_PATH = os.environ.get("GVL_LIB_PATH") or os.path.join(_HERE, "libgvl_msda.so")
-ABI_VERSION = 19          # include/gvl_msda.h GVL_MSDA_ABI_VERSION
+ABI_VERSION = 20          # include/gvl_msda.h GVL_MSDA_ABI_VERSION
 _lock = threading.Lock()
 _lib = None
 
@@ -145,6 +145,10 @@ SIGNATURES = {
     "gvl_lsap_solve_f32": (_I, [_P, _I64, _I64, _P, _P]),
     "gvl_lsap_batch_device_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gvl_hungarian_batch_f32": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I]),
+    "gvl_cl_logits_f32": (_I, [_P, _P, _I64, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "gvl_cl_loss_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "gvl_cl_loss_forward_f32": (_I, [_P] * 5 + [_I] * 7 + [ctypes.c_float] + [_I] * 3 + [_P] * 9 + [_SZ, _P]),
+    "gvl_cl_loss_backward_f32": (_I, [_P] * 10 + [_P, _I64] + [_P] * 4 + [_I] * 5 + [ctypes.c_float] + [_P] * 4),
 }
 
 

@@ -24,6 +24,14 @@ _COMMON = dict(
     optimizer_type='adam', learning_strategy='multi_step', warm_up_ratio=0.1, learning_rate_decay_start=8,
     learning_rate_decay_every=3, learning_rate_decay_rate=0.5, epoch=30, task_heads_different_lr=False, task_heads_lr=5e-5,
     only_ft_captioner=False,
+    # the contrastive event-text branch (opts.py:205-260 overlaid by cfgs/anet_*_ssvg.yml); enable_contrastive stays False by default
+    text_encoder_learning_strategy='frozen', enable_word_context_modeling=True, word_context_modeling_type='attention_pool',
+    enable_sentence_context_modeling=False, enable_layer_diff_text_feature=False, enable_multilayer_projection=False,
+    disable_cl_proj_layer_share_weight=False, contrastive_hidden_size=128, contrastive_loss_temperature=0.1,
+    enable_cross_video_cl=True, enable_e2t_cl=False, enable_bg_for_cl=False, cl_schedule_time=[0, 2], cl_schedule_val=[0, 0.1],
+    text_feature_dim=768,
+    eval_enable_grounding=True, eval_set_cost_class=0., eval_set_cost_cl=1.0, eval_enable_maximum_matching_for_grounding=False, eval_grounding_cost_alpha=0.25,
+    eval_grounding_cost_gamma=2, eval_disable_contrastive=False, eval_enable_matching_score=False, eval_matching_score_weight=0.0,
 )
 
 CONFIGS = {

@@ -3,7 +3,9 @@
 Host-side PyTorch on the GPU tensors (elementwise work on <= B*Q*few values, kept out of
 hand-kernel scope).  The only collective on the reference's hot path lives here: ``all_reduce(num_boxes)``
 (criterion.py:178-180); it runs over RCCL when a process group exists (data-parallel training, gvl_amd.parallel).
-The contrastive criterion (frozen RoBERTa text branch) is outside the accelerated path and is not built.
+``ContrastiveCriterion`` mirrors pdvc/criterion.py:269-373 (cosine logits between event and sentence embeddings, InfoNCE losses):
+on the GPU in fp32 the logits of all decoder layers, the losses and their gradient are one HIP launch each (gvl_contrastive.hip);
+on the CPU, in fp64 or outside the kernels' range the PyTorch formulation below runs.
 """
 import torch
 import torch.distributed as dist
@@ -405,3 +407,213 @@ class SetCriterion(nn.Module):
                     losses.update({k + f'_{i}': v for k, v in l_dict.items()})
             return losses, last_indices, aux_indices
         return losses, last_indices
+
+
+# ---- contrastive event-text branch (pdvc/criterion.py:269-373) ---------------------------------------------------------------------
+CL_MAX_D, CL_MAX_G = 512, 4096                  # range of the kernels (include/gvl_msda.h: gvl_cl_*)
+
+
+class ClLogits:
+    """cosine logits of all decoder layers as the kernel leaves them, with what the loss' gradient needs: ``out`` (L, E, G [+ 1]) in
+    the layout the matcher reads, the inverse clamped norms, and the tensors they were computed from"""
+
+    def __init__(self, event, text, bg, out, inv_e, inv_t, inv_bg):
+        self.event, self.text, self.bg = event, text, bg            # (L, E, D), (1 or L, G, D), (1, D) or None
+        self.out, self.inv_e, self.inv_t, self.inv_bg = out, inv_e, inv_t, inv_bg
+
+
+def cl_kernel_ok(event, text, bg):
+    """do the kernels serve these tensors?  fp32 on one GPU, 1 <= D <= 512, 1 <= G <= 4096, E >= 1; a wrong dtype or device
+    of ONE of them is the caller's error and raises"""
+    ts = [t_ for t_ in (event, text, bg) if t_ is not None]
+    if len({t_.device for t_ in ts}) != 1 or len({t_.dtype for t_ in ts}) != 1:
+        raise ValueError("contrastive criterion: text, event and background embeddings must share one dtype and device, got "
+                         + ", ".join(f"{t_.dtype} on {t_.device}" for t_ in ts))
+    D = event.shape[-1]
+    return (event.is_cuda and event.dtype == torch.float32 and 1 <= D <= CL_MAX_D and 1 <= text.shape[-2] <= CL_MAX_G
+            and event.shape[-2] >= 1 and event.shape[0] * event.shape[-2] * (text.shape[-2] + 1) < 2 ** 31)
+
+
+@torch.no_grad()
+def cl_logits_layers(event, text, bg):
+    """gvl_cl_logits_f32: event (L, E, D), text (1 or L, G, D), bg (1, D) or None -> ClLogits.  One launch for all layers."""
+    with torch.autocast("cuda", enabled=False):
+        ev, tx = event.detach().contiguous(), text.detach().contiguous()
+        b = None if bg is None else bg.detach().contiguous()
+        L, E, D = ev.shape
+        G = tx.shape[1]
+        out = torch.empty((L, E, G + (b is not None)), dtype=torch.float32, device=ev.device)
+        inv_e = torch.empty((L, E), dtype=torch.float32, device=ev.device)
+        inv_t = torch.empty((L, G), dtype=torch.float32, device=ev.device)
+        inv_bg = torch.empty(1, dtype=torch.float32, device=ev.device)
+        with torch.cuda.device(ev.device):
+            rc = _lib.lib().gvl_cl_logits_f32(ev.data_ptr(), tx.data_ptr(), 0 if tx.shape[0] == 1 else G * D,
+                                              None if b is None else b.data_ptr(), L, E, G, D, out.data_ptr(), inv_e.data_ptr(),
+                                              inv_t.data_ptr(), inv_bg.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "cl_logits")
+    return ClLogits(event, text, bg, out, inv_e, inv_t, inv_bg)
+
+
+class ContrastiveLossFn(torch.autograd.Function):
+    """the contrastive losses of ALL decoder layers as one autograd node: gvl_cl_loss_forward_f32 on the logits the matcher has
+    already read, gvl_cl_loss_backward_f32 for the gradients of the un-normalised event, text and background embeddings"""
+
+    @staticmethod
+    def forward(ctx, event, text, bg, rec, pq, pt, pvid, ptbase, B, Q, temperature, cross, e2t, bgall):
+        L, E, D = event.shape
+        G = text.shape[1]
+        dev = event.device
+        P = pq.shape[1]
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        loss = torch.empty((L, 3), **f32)
+        saved = [torch.empty((L, G), **f32), torch.empty((L, E), **f32), torch.empty((L, G), **i32), torch.empty((L, E), **i32),
+                 torch.empty((L, G), **i32), torch.empty((L, G), **f32), torch.empty((L, E), **f32)]
+        lib = _lib.lib()
+        nbytes = lib.gvl_cl_loss_workspace_bytes(L, E, G)
+        head = 16 * ((L + 3) // 4)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws[:head].zero_()                                                  # the layers' arrival tickets
+        with torch.cuda.device(dev):
+            rc = lib.gvl_cl_loss_forward_f32(rec.out.data_ptr(), pq.data_ptr(), pt.data_ptr(), pvid.data_ptr(),
+                                             None if ptbase is None else ptbase.data_ptr(), L, E, G, int(rec.bg is not None), P, B, Q,
+                                             float(temperature), int(cross), int(e2t), int(bgall), loss.data_ptr(),
+                                             *[s_.data_ptr() for s_ in saved], ws.data_ptr(), nbytes,
+                                             torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "cl_loss_forward")
+        ctx.save_for_backward(event, text, *([bg] if bg is not None else []), rec.out, rec.inv_e, rec.inv_t, rec.inv_bg, *saved)
+        ctx.has_bg, ctx.Q, ctx.temperature = bg is not None, Q, float(temperature)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        t_ = list(ctx.saved_tensors)
+        event, text = t_[0], t_[1]
+        bg = t_[2] if ctx.has_bg else None
+        out, inv_e, inv_t, inv_bg, lse_t, lse_e, ev_of_col, col_of_ev, vid_of_col, wcol, wev = t_[2 + ctx.has_bg:]
+        L, E, D = event.shape
+        G = text.shape[1]
+        ev, tx = event.contiguous(), text.contiguous()
+        b = None if bg is None else bg.contiguous()
+        gl = grad_loss[:, 0].contiguous()               # (the t2e / e2t columns are reported, not differentiated)
+        g_event, g_text = torch.empty_like(ev), torch.empty_like(tx)
+        g_bg = None if b is None else torch.empty_like(b)
+        with torch.cuda.device(ev.device):
+            rc = _lib.lib().gvl_cl_loss_backward_f32(
+                gl.data_ptr(), out.data_ptr(), lse_t.data_ptr(), lse_e.data_ptr(), ev_of_col.data_ptr(), col_of_ev.data_ptr(),
+                vid_of_col.data_ptr(), wcol.data_ptr(), wev.data_ptr(), ev.data_ptr(), tx.data_ptr(),
+                0 if tx.shape[0] == 1 else G * D, None if b is None else b.data_ptr(), inv_e.data_ptr(), inv_t.data_ptr(),
+                inv_bg.data_ptr(), L, E, G, D, ctx.Q, ctx.temperature, g_event.data_ptr(), g_text.data_ptr(),
+                None if b is None else g_bg.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "cl_loss_backward")
+        return (g_event, g_text, g_bg) + (None,) * 11
+
+
+class ContrastiveCriterion(nn.Module):
+    """criterion.py:269-373.  ``forward_logits`` / ``forward`` / ``_preprocess`` keep the reference's signatures; ``logits_layers`` /
+    ``loss_layers`` are the all-layers forms PDVC.forward uses (one launch each)."""
+
+    def __init__(self, temperature=0.1, enable_cross_video_cl=False, enable_e2t_cl=False, enable_bg_for_cl=False):
+        super().__init__()
+        if enable_e2t_cl and not enable_cross_video_cl:
+            raise NotImplementedError("enable_cross_video_cl=False with enable_e2t_cl=True: the reference itself fails there "
+                                      "(criterion.py:331 hands a label tensor to torch.arange)")
+        self.temperature = temperature
+        self.enable_cross_video_cl = enable_cross_video_cl
+        self.enable_e2t_cl = enable_e2t_cl
+        self.enable_bg_for_cl = enable_bg_for_cl
+        self.force_torch = False                    # measurement switch (tools/contrastive_timing.py): the PyTorch formulation
+
+    # -- the PyTorch formulation (CPU, fp64, sizes outside the kernels' range) --------------------------------------------------
+    @staticmethod
+    def _torch_logits(text, event, bg=None):
+        en = F.normalize(event, p=2, dim=1)
+        logits = F.normalize(text, p=2, dim=1) @ en.t()
+        if bg is not None:
+            logits = torch.cat((logits, (en * F.normalize(bg, p=2, dim=1)).sum(dim=1)[None]), dim=0)
+        return logits
+
+    def _torch_loss(self, text, event, labels, counts, B, Q, bg):
+        """text (M, D): the matched sentences in pair order; labels (M): their events (rows of `event`, or query ids per video)"""
+        raw = self._torch_logits(text, event)
+        x = raw / self.temperature
+        if self.enable_cross_video_cl:
+            loss = F.cross_entropy(x, labels)
+            if self.enable_e2t_cl:
+                M, E = x.shape
+                owner = torch.full((E,), M, dtype=torch.long, device=x.device)
+                owner = owner.scatter_reduce(0, labels, torch.arange(M, device=x.device), reduce="amin", include_self=True)
+                bg_row = (F.normalize(event, p=2, dim=1) * F.normalize(bg, p=2, dim=1)).sum(dim=1) / self.temperature
+                x2 = torch.cat((x, bg_row[None]), dim=0).t()
+                if not self.enable_bg_for_cl:
+                    keep = owner < M
+                    x2, owner = x2[keep], owner[keep]
+                loss = 0.5 * (loss + F.cross_entropy(x2, owner))
+            return loss, raw
+        total, base = 0, 0
+        for i in range(B):
+            n = counts[i]
+            total = total + F.cross_entropy(x[base:base + n, i * Q:(i + 1) * Q], labels[base:base + n])
+            base += n
+        return total / B, raw
+
+    # -- reference API ------------------------------------------------------------------------------------------------------------
+    def forward_logits(self, text_embed, event_embed, bg_embed=None):
+        """(G, D), (E, D)[, (1, D)] -> (G [+ 1], E) cosines"""
+        needs_grad = torch.is_grad_enabled() and any(t_ is not None and t_.requires_grad for t_ in (text_embed, event_embed, bg_embed))
+        if self.force_torch or needs_grad or not cl_kernel_ok(event_embed, text_embed, bg_embed):
+            return self._torch_logits(text_embed, event_embed, bg_embed)
+        return cl_logits_layers(event_embed[None], text_embed[None], bg_embed).out[0].t()
+
+    def _preprocess(self, event_embed, text_embed, matching_indices):
+        batch_size, max_event_num, f_dim = event_embed.shape
+        labels, texts, counts = [], [], []
+        for i in range(batch_size):
+            base = i * max_event_num if self.enable_cross_video_cl else 0
+            feat_ids, cap_ids = matching_indices[i]
+            counts.append(len(feat_ids))
+            texts.append(text_embed[i][cap_ids])
+            labels.append(feat_ids + base)
+        return (event_embed.view(-1, f_dim), torch.cat(texts, dim=0), torch.cat(labels, dim=0).to(event_embed.device), counts)
+
+    def forward(self, text_embed, event_embed, matching_indices, return_logits=False, bg_embed=None):
+        """text_embed: per video (n_i, D); event_embed (B, Q, D); matching_indices: per video (query ids, caption ids)"""
+        B, Q, D = event_embed.shape
+        if self.enable_e2t_cl and bg_embed is None:
+            raise TypeError("ContrastiveCriterion: enable_e2t_cl needs bg_embed (the reference normalises None here, criterion.py:313)")
+        text = torch.cat(list(text_embed), dim=0)
+        n_pairs = sum(len(f_) for f_, _ in matching_indices)
+        if self.force_torch or n_pairs == 0 or not cl_kernel_ok(event_embed, text, bg_embed):
+            event, rows, labels, counts = self._preprocess(event_embed, text_embed, matching_indices)
+            loss, raw = self._torch_loss(rows, event, labels, counts, B, Q, bg_embed)
+            return (loss, raw) if return_logits else loss
+        offs, q, c, v = 0, [], [], []
+        for i, (feat_ids, cap_ids) in enumerate(matching_indices):
+            q.append(torch.as_tensor(feat_ids, dtype=torch.int64).cpu())
+            c.append(torch.as_tensor(cap_ids, dtype=torch.int64).cpu() + offs)
+            v.append(torch.full((len(feat_ids),), i, dtype=torch.int64))
+            offs += len(text_embed[i])
+        packed = torch.stack([torch.cat(q), torch.cat(c), torch.cat(v)]).to(event_embed.device)
+        rec = self.logits_layers(text[None], event_embed.reshape(1, B * Q, D), bg_embed)
+        loss = self.loss_layers(rec, packed[0][None], packed[1][None], packed[2], None, B, Q)[0]
+        if return_logits:
+            return loss, rec.out[0].index_select(1, packed[1]).t()
+        return loss
+
+    # -- all decoder layers at once ---------------------------------------------------------------------------------------------
+    def kernels_serve(self, text, event, bg=None):
+        return not self.force_torch and cl_kernel_ok(event, text, bg)
+
+    def logits_layers(self, text, event, bg=None):
+        """text (1 or L, G, D), event (L, E, D), bg (1, D) or None -> ClLogits; .out[l] is forward_logits(...).t() of layer l"""
+        return cl_logits_layers(event, text, bg)
+
+    def loss_layers(self, rec, pair_q, pair_t, pair_vid, pair_tbase, B, Q):
+        """pair_q / pair_t (L, P) int64: matched query of its video / text row (minus pair_tbase) of every pair and layer,
+        pair_vid (P) -> (L,) losses on ONE autograd node"""
+        with torch.autocast("cuda", enabled=False):
+            table = ContrastiveLossFn.apply(rec.event, rec.text, rec.bg, rec, pair_q.contiguous(), pair_t.contiguous(),
+                                            pair_vid.contiguous(), None if pair_tbase is None else pair_tbase.contiguous(), B, Q,
+                                            self.temperature, self.enable_cross_video_cl, self.enable_e2t_cl, self.enable_bg_for_cl)
+        return table[:, 0]

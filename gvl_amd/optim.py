@@ -189,8 +189,13 @@ def build_optimizer(model, opt, params=None, **torch_kwargs):
     parameters (the rest still has gradients, which the step clips with them: train.py:407).  `params` (default: the model's
     parameters) is what "everything" means; options missing from `opt` take the reference's defaults (opts.py), so an older
     Namespace still gives Adam with one group.  torch_kwargs (capturable, fused, ...) go to the torch optimizer.  The
-    contrastive text encoder, ft_captioner_from_scratch and only_ft_class_head are out of scope."""
+    frozen text encoder of a contrastive model is left out (train.py:242-246); the word-level pool, the contrastive projections
+    and the background embedding are ordinary parameters of "everything".  ft_captioner_from_scratch and only_ft_class_head are
+    out of scope."""
     other = [p for p in (model.parameters() if params is None else params)]
+    if getattr(model, "text_encoder", None) is not None:
+        frozen = {id(p) for p in model.text_encoder.parameters()}
+        other = [p for p in other if id(p) not in frozen]
     if getattr(opt, "only_ft_captioner", False):
         other = model.captioner_parameters()
     if getattr(opt, "task_heads_different_lr", False):
@@ -241,3 +246,24 @@ def build_scheduler(opt, optimizer, total_steps):
         milestones = [start + every * k for k in range(int((getattr(opt, "epoch", 30) - start) / every))]
         return torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones, gamma=getattr(opt, "learning_rate_decay_rate", 0.5))
     raise NotImplementedError(f"learning_strategy {strategy!r}")
+
+
+def contrastive_weight(opt, epoch):
+    """the weight of the contrastive losses in force at `epoch` (train.py:304-311,363-368): cl_schedule_val[i] from epoch
+    cl_schedule_time[i] on"""
+    times, vals = list(opt.cl_schedule_time), list(opt.cl_schedule_val)
+    weight = 0.0
+    for t_, v in zip(times, vals):
+        if epoch >= t_:
+            weight = v
+    return weight
+
+
+def apply_contrastive_schedule(criterion, opt, epoch):
+    """train.py:343-346,363-368: every contrastive_loss* weight of the set criterion, and the matcher's cost_cl -- 0 while the weight is 0"""
+    weight = contrastive_weight(opt, epoch)
+    for key in criterion.weight_dict:
+        if 'contrastive_loss' in key:
+            criterion.weight_dict[key] = weight
+    criterion.matcher.cost_cl = 0 if weight == 0 else opt.set_cost_cl
+    return weight

@@ -214,11 +214,18 @@ class TrainStep:
     """zero_grad -> forward -> weighted loss -> backward (+ overlapped all-reduce) -> clip -> Adam (train.py:385-409)"""
 
     def __init__(self, model, criterion, opt, world_size=1, process_group=None, capturable=False, flat=None,
-                 overlap=True, autocast_dtype=None, first=None):
-        """autocast_dtype (e.g. torch.bfloat16): forward + losses under torch.autocast -- bf16 GEMMs and bf16-storage
+                 overlap=True, autocast_dtype=None, first=None, contrastive_criterion=None):
+        """contrastive_criterion: of a model built with enable_contrastive (default: one built from model.opt).
+        autocast_dtype (e.g. torch.bfloat16): forward + losses under torch.autocast -- bf16 GEMMs and bf16-storage
         deformable attention, fp32 master weights / Adam, fp32 islands for the teacher-forced captioner loop and the
         criterion kernels."""
         self.model, self.criterion, self.opt = model, criterion, opt
+        if getattr(model, "enable_contrastive", False) and contrastive_criterion is None:
+            from .criterion import ContrastiveCriterion
+            o = vars(model.opt)
+            contrastive_criterion = ContrastiveCriterion(o.get('contrastive_loss_temperature', 0.1), o.get('enable_cross_video_cl', True),
+                                                         o.get('enable_e2t_cl', False), o.get('enable_bg_for_cl', False))
+        self.contrastive_criterion = contrastive_criterion
         self.autocast_dtype = autocast_dtype
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.buckets = GradBuckets(self.params, process_group=process_group, flat=flat, overlap=overlap, first=first)
@@ -266,7 +273,7 @@ class TrainStep:
         # same precaution torch.cuda.make_graphed_callables takes
         with torch.autocast("cuda", dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None,
                             cache_enabled=False):
-            out, loss = self.model(dt, self.criterion, None, self.opt.transformer_input_type)
+            out, loss = self.model(dt, self.criterion, self.__dict__.get("contrastive_criterion"), self.opt.transformer_input_type)
         from .criterion import weighted_loss_sum
         return weighted_loss_sum(loss, self.criterion.weight_dict, self.__dict__.setdefault("_loss_weights", {})), loss
 
@@ -326,6 +333,8 @@ class GraphedTrainStep(TrainStep):
         of 4, 9.50 of 2, 9.46 of 1.  (Rounds 2-3 measured the opposite, 11.8 against 11.0 ms: the captures after
         the first recorded waits on the previous capture's still-alive autograd nodes -- TrainStep returned its loss values
         attached -- and "bucket" replays exactly those later captures.)"""
+        if getattr(model, "enable_contrastive", False):
+            raise NotImplementedError("contrastive branch: captured steps not built")
         from . import graph_replay_guard
         graph_replay_guard("GraphedTrainStep")
         self.split = (world_size > 1) if split_exchange is None else bool(split_exchange)
@@ -618,6 +627,8 @@ class GraphedEvalForward:
 
     def __init__(self, model, criterion, transformer_input_type="queries", warmup=1, autocast_dtype=None,
                  max_graphs=4, max_gt=0, decode_chunk=5, padded=None):
+        if getattr(model, "enable_contrastive", False):
+            raise NotImplementedError("contrastive branch: captured steps not built")
         from . import graph_replay_guard
         graph_replay_guard("GraphedEvalForward")
         self.model, self.criterion, self.kind = model, criterion, transformer_input_type

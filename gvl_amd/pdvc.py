@@ -3,10 +3,15 @@
 Mirrors pdvc/pdvc.py:41-314 (model + forward), :434-519 (eval: parallel_prediction_full), :540-660 (train:
 parallel_prediction_matched), :699-884 (caption_prediction / caption_prediction_eval) and :1181-1238 (build), for the
 configuration space of BASELINE.json: ``transformer_input_type='queries'``, LSTM-DSA captioner
-(``caption_decoder_type: standard``), ``enable_contrastive=False`` (the contrastive branch needs the frozen RoBERTa
-text encoder, which SURVEY.md section 2 row 15 places outside the accelerated path -- requesting it raises).
+(``caption_decoder_type: standard``).  ``enable_contrastive=True`` builds the contrastive event-text branch of the ``*_ssvg``
+configurations (pdvc.py:62-109,148-165,211-248: word-level pool, the two projections, the background embedding, the cosine
+logits in the matcher cost, the InfoNCE losses) around a FROZEN text encoder that the caller passes in -- any module with the
+encoder's interface, e.g. ``gvl_amd.text.PrecomputedTextEncoder`` over pre-extracted features; no weights are downloaded and
+``transformers`` is never imported.  Not built, each raising NotImplementedError with its switch:
+``enable_sentence_context_modeling`` (needs HF BertEncoder), a text encoder that is not frozen, ``caption_loss_type='rl'``.
 Sub-module and parameter names equal the reference's (``base_encoder, transformer, caption_head.N, query_embed,
-class_head.N, count_head.N, bbox_head.N.layers.K``) so reference checkpoints load with ``strict=True``;
+class_head.N, count_head.N, bbox_head.N.layers.K, text_encoder, word_context_model, contrastive_projection_event.N,
+contrastive_projection_text.N, background_embed``) so reference checkpoints load with ``strict=True``;
 ``PDVC.forward(dt, criterion, contrastive_criterion, transformer_input_type, eval_mode)`` returns the same
 ``(out, loss)`` dictionaries.
 """
@@ -21,7 +26,7 @@ from torch import nn
 
 from .base_encoder import build_base_encoder
 from .CaptioningHead import build_captioner
-from .criterion import SetCriterion, unbind_tagged
+from .criterion import ContrastiveCriterion, SetCriterion, unbind_tagged
 from .deformable_transformer import build_deforamble_transformer, inverse_sigmoid
 from .linear import Linear
 from .matcher import build_matcher
@@ -95,12 +100,30 @@ class PDVC(nn.Module):
     def __init__(self, base_encoder, text_encoder, transformer, captioner, num_classes, num_queries,
                  num_feature_levels, aux_loss=True, with_box_refine=False, opt=None, translator=None):
         super().__init__()
-        if opt.enable_contrastive or text_encoder is not None:
-            raise NotImplementedError("gvl_amd.PDVC: the contrastive text branch (frozen RoBERTa) is outside the "
-                                      "accelerated path; build with enable_contrastive=False")
         self.opt = opt
-        self.enable_contrastive = False
+        o = vars(opt)
+        self.enable_contrastive = bool(o.get('enable_contrastive', False))
+        self.enable_layer_diff_text_feature = bool(o.get('enable_layer_diff_text_feature', False))
+        self.enable_word_context_modeling = bool(o.get('enable_word_context_modeling', False))
+        self.enable_sentence_context_modeling = bool(o.get('enable_sentence_context_modeling', False))
+        if self.enable_contrastive:
+            if text_encoder is None:
+                raise ValueError("gvl_amd.PDVC: enable_contrastive=True needs a text_encoder module")
+            if self.enable_sentence_context_modeling:
+                raise NotImplementedError("enable_sentence_context_modeling=True is not built (it needs HuggingFace's BertEncoder; "
+                                          "gvl_amd does not import transformers)")
+            if o.get('text_encoder_learning_strategy', 'frozen') != 'frozen':
+                raise NotImplementedError("text_encoder_learning_strategy != 'frozen' is not built: the text encoder runs under "
+                                          "no_grad with its parameters frozen")
+            if o.get('caption_loss_type', 'ce') == 'rl':
+                raise NotImplementedError("caption_loss_type='rl' is not built with the contrastive branch")
         self.base_encoder = base_encoder
+        num_pred_text = 0
+        if self.enable_contrastive or text_encoder is not None:
+            self.text_encoder = text_encoder
+            for p_ in text_encoder.parameters():
+                p_.requires_grad_(False)
+            num_pred_text += 1
         self.transformer = transformer
         self.caption_head = captioner
         hidden_dim = transformer.d_model
@@ -111,6 +134,27 @@ class PDVC(nn.Module):
             self.class_head = nn.Linear(hidden_dim, num_classes)
         self.count_head = nn.Linear(hidden_dim, opt.max_eseq_length + 1)
         self.bbox_head = MLP(hidden_dim, hidden_dim, 2, 3)
+        if self.enable_contrastive:                                                    # pdvc.py:82-109
+            from .text import WordLevelContextModeling, max_pool_words, mean_pool_words
+            text_dim = self.text_encoder.config.hidden_size
+            self.sentence_context_model = None
+            self.word_context_model = None
+            if self.enable_word_context_modeling:
+                kind = o.get('word_context_modeling_type', 'attention_pool')
+                pools = {'max_pool': max_pool_words, 'mean_pool': mean_pool_words}
+                if kind == 'attention_pool':
+                    self.word_context_model = WordLevelContextModeling(text_dim)
+                elif kind in pools:
+                    self.__dict__['word_context_model'] = pools[kind]          # (a function, not a sub-module)
+                else:
+                    raise ValueError(f"word_context_modeling_type {kind!r}")
+            cl_dim = opt.contrastive_hidden_size
+            if o.get('enable_multilayer_projection', False):
+                self.contrastive_projection_event = MLP(hidden_dim, hidden_dim, cl_dim, 2)
+                self.contrastive_projection_text = MLP(text_dim, text_dim, cl_dim, 2)
+            else:
+                self.contrastive_projection_event = nn.Linear(hidden_dim, cl_dim)
+                self.contrastive_projection_text = nn.Linear(text_dim, cl_dim)
         self.num_feature_levels = num_feature_levels
         self.aux_loss = aux_loss
         self.with_box_refine = with_box_refine
@@ -143,9 +187,20 @@ class PDVC(nn.Module):
             self.count_head = nn.ModuleList([self.count_head for _ in range(num_pred)])
             self.bbox_head = nn.ModuleList([self.bbox_head for _ in range(num_pred)])
             self.transformer.decoder.bbox_head = None
+        if self.enable_contrastive:                                                    # pdvc.py:148-156
+            if o.get('disable_cl_proj_layer_share_weight', False):
+                self.contrastive_projection_event = _clones(self.contrastive_projection_event, num_pred)
+                self.contrastive_projection_text = _clones(self.contrastive_projection_text, num_pred_text)
+            else:
+                self.contrastive_projection_event = nn.ModuleList([self.contrastive_projection_event for _ in range(num_pred)])
+                self.contrastive_projection_text = nn.ModuleList([self.contrastive_projection_text
+                                                                  for _ in range(num_pred_text)])
         self.translator = translator
         self.disable_mid_caption_heads = opt.disable_mid_caption_heads
-        self.background_embed = None
+        if o.get('enable_e2t_cl', False):                 # (as the reference: whenever the switch is set, pdvc.py:162-165)
+            self.background_embed = nn.Parameter(torch.randn(1, opt.contrastive_hidden_size), requires_grad=True)
+        else:
+            self.background_embed = None
 
     # -- parameter groups used by train.py (pdvc.py:170-209) ---------------------------------------------------
     def get_filter_rule_for_encoder(self):
@@ -170,6 +225,104 @@ class PDVC(nn.Module):
         for name, p in self.named_parameters():
             (enc if rule(name) else dec).append(p)
         return enc, dec
+
+    # -- contrastive branch -----------------------------------------------------------------------------------------
+    def train(self, mode=True):
+        super().train(mode)
+        if getattr(self, "text_encoder", None) is not None:
+            self.text_encoder.eval()                       # frozen: no dropout in the encoder, whatever the model's mode
+        return self
+
+    def text_encoding(self, text_encoder_input, gt_cap_num, memory=None, enable_sentence_context_modeling=False):
+        """pdvc.py:211-248 -> (text_embed, word_embed, cross_attention_scores, pre_proj_embed); text_embed = [aux layers'
+        sentence embeddings per video, last layer's]"""
+        dtype = next(self.parameters()).dtype
+        with torch.no_grad():
+            enc = self.text_encoder(**text_encoder_input)
+        word_embed = enc.last_hidden_state.to(dtype=dtype)
+        if self.enable_word_context_modeling:
+            sent = self.word_context_model(word_embed, text_encoder_input['attention_mask'])
+        else:
+            sent = enc['pooler_output'].to(dtype=dtype)
+        attention_pool = vars(self.opt).get('word_context_modeling_type', 'attention_pool') == 'attention_pool'
+        # the projections run ONCE over all sentences of the batch; the per-video lists are views of the result
+        sizes = [int(n) for n in gt_cap_num]
+        feats = list(sent.split(sizes))
+        text_feature = list(self.contrastive_projection_text[-1](sent).split(sizes))
+        if self.enable_layer_diff_text_feature:
+            aux = sent if attention_pool else F.gelu(sent)
+            aux_feats = list(aux.split(sizes))
+            aux_feature = list(self.contrastive_projection_text[0](aux).split(sizes))
+        else:
+            aux_feats, aux_feature = feats, text_feature
+        return [aux_feature, text_feature], word_embed, [], [aux_feats, feats]
+
+    def _expand_text(self, others, num_pred):
+        """pdvc.py:477-482: the two-element text list -> one entry per decoder layer"""
+        te = others['text_embed']
+        if len(te) < num_pred:
+            raw, ctx = te
+            others['text_embed'] = te = [raw] * (num_pred - 1) + [ctx]
+        assert len(te) == num_pred, 'visual features have {} levels, but text have {}'.format(num_pred, len(te))
+        return te
+
+    def _cl_match_mats(self, contrastive_criterion, others, num_pred):
+        """cl_match_mats of every decoder layer (pdvc.py:484-489): (E, G [+ 1]) cosines, background column last.  On the GPU in
+        fp32 ONE launch for all layers (what it leaves is kept for the loss: others['_cl_rec']); else the op sequence."""
+        te = self._expand_text(others, num_pred)
+        event = others['event_embed']
+        ev = event.reshape(num_pred, -1, event.shape[-1])
+        shared = all(t_ is te[0] for t_ in te)
+        cats = [torch.cat(te[0], dim=0)] if shared else [torch.cat(t_, dim=0) for t_ in te]
+        bg = self.background_embed
+        if cats[0].shape[0] > 0 and contrastive_criterion.kernels_serve(cats[0], ev, bg):
+            with torch.autocast("cuda", enabled=False):
+                text = cats[0][None] if shared else torch.stack(cats)
+                rec = contrastive_criterion.logits_layers(text.float(), ev.float(), None if bg is None else bg.float())
+            others['_cl_rec'] = rec
+            return list(rec.out.unbind(0))
+        others['_cl_rec'] = None
+        with torch.no_grad():
+            return [contrastive_criterion.forward_logits(cats[0 if shared else l], ev[l], bg).t() for l in range(num_pred)]
+
+    def _contrastive_losses(self, contrastive_criterion, others, layers, matches, loss, out, with_bg=True, return_logits=False):
+        """contrastive_loss[_l] of the given decoder layers (pdvc.py:520-536,627-638,656-664)"""
+        num_pred = others['event_embed'].shape[0]
+        te = others['text_embed']
+        event = others['event_embed']
+        B, Q = event.shape[1:3]
+        bg = self.background_embed if with_bg else None
+        rec = others.get('_cl_rec')
+        device_matches = all(hasattr(m, "plan") and not getattr(m.plan, "padded", False) for m in matches)
+        # (without bg_embed -- the reference's aux_loss=False training call -- only when there is no background row to leave out)
+        if (rec is not None and device_matches and (with_bg or rec.bg is None) and len(te) == num_pred and matches[0].plan.t1 > 0
+                and sum(len(t_) for t_ in te[0]) == sum(matches[0].plan.sizes)):
+            plan = matches[0].plan
+            t1 = plan.t1
+            # (the matcher's own result buffers are ordered last layer first: the pairs are taken per layer, in decoder order)
+            pq, pt = torch.stack([m.q for m in matches]), torch.stack([m.t for m in matches])
+            if len(layers) == num_pred:
+                use = rec
+            else:                                                   # (aux_loss=False: the last layer alone)
+                from .criterion import ClLogits
+                li = layers if rec.text.shape[0] > 1 else [0]
+                use = ClLogits(rec.event[layers], rec.text[li], rec.bg, rec.out[layers].contiguous(), rec.inv_e[layers].contiguous(),
+                               rec.inv_t[layers].contiguous(), rec.inv_bg)
+            vec = contrastive_criterion.loss_layers(use, pq, pt, plan.vid_of_entry, plan.tgt_base, B, Q)
+            parts = unbind_tagged(vec)
+            for k, l_id in enumerate(layers):
+                loss['contrastive_loss' if l_id == num_pred - 1 else f'contrastive_loss_{l_id}'] = parts[k]
+            if return_logits:
+                out['cl_logits'] = use.out[-1].index_select(1, (matches[-1].t + plan.tgt_base)).t()
+            return
+        for l_id, m in zip(layers, matches):
+            indices = m if isinstance(m, list) else m[0]
+            kw = {'bg_embed': bg} if with_bg else {}
+            res = contrastive_criterion(text_embed=te[l_id], event_embed=event[l_id], matching_indices=indices,
+                                        return_logits=return_logits, **kw)
+            if return_logits:
+                res, out['cl_logits'] = res
+            loss['contrastive_loss' if l_id == num_pred - 1 else f'contrastive_loss_{l_id}'] = res
 
     # -- the hot path ---------------------------------------------------------------------------------------------
     def encode(self, dt):
@@ -201,6 +354,11 @@ class PDVC(nn.Module):
         return side
 
     def supports_padded_targets(self, criterion, eval_mode, batch=None, slots=None):
+        if self.enable_contrastive:               # the contrastive cost term and losses read the list-form targets
+            return False
+        return self._supports_padded_targets(criterion, eval_mode, batch, slots)
+
+    def _supports_padded_targets(self, criterion, eval_mode, batch=None, slots=None):
         """Can a step on this model run in the layout-independent form (dt['_gvl_targets'] = PaddedTargets; what
         gvl_amd.parallel's captured steps use)?  Eval: whenever the criterion can.  Train: additionally the caption
         losses of all decoder layers must come from the one-pass teacher-forced path (caption_prediction_layers).
@@ -240,6 +398,8 @@ class PDVC(nn.Module):
 
     def forward(self, dt, criterion, contrastive_criterion, transformer_input_type, eval_mode=False):
         from . import linear as _linear
+        if self.enable_contrastive and dt.get('_gvl_targets') is not None:
+            raise NotImplementedError("contrastive branch: captured steps not built")
         if (self.training and torch.is_grad_enabled() and torch.is_autocast_enabled() and dt['video_tensor'].is_cuda
                 and _linear.train_linear_enabled() and autocast_training_policy() != "bf16"):
             # TRAINING under torch.autocast: the hand-written training path at one (or three) fp16 products per fp32 product
@@ -305,9 +465,15 @@ class PDVC(nn.Module):
         hs, inter_references = self.transformer.forward_decoder(tgt, reference_points, memory, tshapes, lsi,
                                                                 valid_ratios, query_embed, mask_flat, proposals_mask,
                                                                 disable_refine)
+        text_embed = pre_proj = None
+        event_embed = hs
+        if self.enable_contrastive:                                               # pdvc.py:279-289
+            if dt.get('text_encoder_input'):
+                text_embed, _, _, pre_proj = self.text_encoding(dt['text_encoder_input'], [len(s_) for s_ in dt['cap_raw']], memory)
+            event_embed = torch.stack([self.contrastive_projection_event[i](hs_i) for i, hs_i in enumerate(hs.unbind(0))])
         others = {'memory': memory, 'mask_flatten': mask_flat, 'spatial_shapes': tshapes, 'level_start_index': lsi,
-                  'valid_ratios': valid_ratios, 'proposals_mask': proposals_mask, 'text_embed': None,
-                  'event_embed': hs, 'pre_proj_text_embed': None}
+                  'valid_ratios': valid_ratios, 'proposals_mask': proposals_mask, 'text_embed': text_embed,
+                  'event_embed': event_embed, 'pre_proj_text_embed': pre_proj}
         if eval_mode or self.opt.caption_loss_coef == 0:
             return self.parallel_prediction_full(dt, criterion, contrastive_criterion, hs, query_embed,
                                                  init_reference, inter_references, others, disable_refine,
@@ -422,7 +588,11 @@ class PDVC(nn.Module):
             if torch.is_grad_enabled():
                 self.transformer.decoder.__dict__["_gvl_coords"] = None       # (see parallel_prediction_matched)
             all_out = self._pack(hs, classes, counts, coords, cap_probs, seqs)
+            if self.enable_contrastive:                         # (on the stream the criterion runs on, before it)
+                all_out['cl_match_mats'] = self._cl_match_mats(contrastive_criterion, others, num_pred)
             all_out['event_embed'] = others['event_embed']
+            if others['text_embed'] is not None:
+                all_out['text_embed'] = others['text_embed']
             all_out['event_feat'] = hs
             out = {k: v[-1] for k, v in all_out.items()}
             if self.aux_loss:
@@ -430,7 +600,11 @@ class PDVC(nn.Module):
                 out['aux_outputs'] = [{k: all_out[k][j] for k in keys} for j in range(num_pred - 1)]
             if criterion is None:                               # pure-inference use (bench / graph capture)
                 return out, {}
-            loss, last_indices, *_ = criterion(out, targets)
+            loss, last_indices, *aux_indices = criterion(out, targets)
+            if self.enable_contrastive:                         # pdvc.py:520-536
+                layers = list(range(num_pred)) if self.aux_loss else [num_pred - 1]
+                matches = [last_indices if l_id == num_pred - 1 else aux_indices[0][l_id] for l_id in layers]
+                self._contrastive_losses(contrastive_criterion, others, layers, matches, loss, out, return_logits=True)
             return out, loss
 
         targets = self._targets(dt) if criterion is not None else None
@@ -499,6 +673,8 @@ class PDVC(nn.Module):
         # graph kept alive across iterations makes the next backward wait on the old AccumulateGrad streams: +1.5 ms)
         self.transformer.decoder.__dict__["_gvl_coords"] = None
         all_out = self._pack(hs, classes, counts, coords, cap_probs, seqs)
+        if self.enable_contrastive and self.opt.set_cost_cl > 0:                  # pdvc.py:575-588
+            all_out['cl_match_mats'] = self._cl_match_mats(contrastive_criterion, others, num_pred)
         out = {k: v[-1] for k, v in all_out.items()}
         if self.aux_loss:
             keys = list(all_out.keys())
@@ -511,6 +687,10 @@ class PDVC(nn.Module):
             layers = [num_pred - 1]
         layers = list(layers)
         matches = [last_indices if l_id == num_pred - 1 else aux_indices[l_id] for l_id in layers]
+        if self.enable_contrastive:
+            # pdvc.py:627-638; aux_loss=False (:656-664): the reference's call carries no bg_embed and reads the UN-expanded
+            # two-element text list when set_cost_cl == 0 -- both kept as they are
+            self._contrastive_losses(contrastive_criterion, others, layers, matches, loss, out, with_bg=self.aux_loss)
         refs = [init_reference if l_id == 0 else inter_references[l_id - 1] for l_id in layers]
         if getattr(matches[0], "plan", None) is not None and getattr(matches[0].plan, "padded", False):
             if not self._one_pass_captioning(layers, matches, hs, None):
@@ -743,15 +923,25 @@ class PDVC(nn.Module):
         return cap_loss.mean(), probs, seq
 
 
-def build(args):
-    """pdvc.py:1181-1238 -> (model, criterion, contrastive_criterion, postprocessors)."""
-    if args.enable_contrastive:
-        raise NotImplementedError("gvl_amd.pdvc.build: enable_contrastive=True needs the frozen RoBERTa text encoder "
-                                  "(out of the accelerated path); set enable_contrastive=False")
+def build(args, text_encoder=None):
+    """pdvc.py:1181-1238 -> (model, criterion, contrastive_criterion, postprocessors).  enable_contrastive: the frozen text encoder
+    is the module passed as `text_encoder`, or gvl_amd.text.PrecomputedTextEncoder(args.text_feature_dim) for pre-extracted
+    features; nothing is downloaded."""
+    o = vars(args)
+    if o.get('enable_contrastive', False) and text_encoder is None:
+        if o.get('text_feature_dim'):
+            from .text import PrecomputedTextEncoder
+            text_encoder = PrecomputedTextEncoder(args.text_feature_dim)
+        else:
+            raise ValueError("gvl_amd.pdvc.build: enable_contrastive=True needs a text encoder -- pass build(args, text_encoder=module) "
+                             "(any module with the encoder's interface), or set args.text_feature_dim to run on pre-extracted "
+                             "features through gvl_amd.text.PrecomputedTextEncoder")
+    if not o.get('enable_contrastive', False):
+        text_encoder = None
     base_encoder = build_base_encoder(args)
     transformer = build_deforamble_transformer(args)
     captioner = build_captioner(args)
-    model = PDVC(base_encoder, None, transformer, captioner, num_classes=args.num_classes,
+    model = PDVC(base_encoder, text_encoder, transformer, captioner, num_classes=args.num_classes,
                  num_queries=args.num_queries, num_feature_levels=args.num_feature_levels, aux_loss=args.aux_loss,
                  with_box_refine=args.with_box_refine, opt=args)
     matcher = build_matcher(args)
@@ -767,4 +957,11 @@ def build(args):
                              focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, opt=args)
     criterion.to(torch.device(args.device))
     postprocessors = {'bbox': PostProcess(args)}
-    return model, criterion, None, postprocessors
+    contrastive_criterion = None
+    if o.get('enable_contrastive', False):
+        contrastive_criterion = ContrastiveCriterion(temperature=o.get('contrastive_loss_temperature', 0.1),
+                                                     enable_cross_video_cl=o.get('enable_cross_video_cl', True),
+                                                     enable_e2t_cl=o.get('enable_e2t_cl', False),
+                                                     enable_bg_for_cl=o.get('enable_bg_for_cl', False))
+        contrastive_criterion.to(torch.device(args.device))
+    return model, criterion, contrastive_criterion, postprocessors

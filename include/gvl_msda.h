@@ -48,8 +48,11 @@
 extern "C" {
 #endif
 
-#define GVL_MSDA_ABI_VERSION 19
+#define GVL_MSDA_ABI_VERSION 20
 /* ABI history (newest first):
+ * 20: + gvl_cl_logits_f32 / gvl_cl_loss_forward_f32 / gvl_cl_loss_backward_f32 / gvl_cl_loss_workspace_bytes (the contrastive
+ *      event-text branch: cosine logits of all decoder layers, the InfoNCE losses and their gradient, one launch each);
+ *      profiling tags GVL_PROF_CL_LOGITS / GVL_PROF_CL_LOSS_FWD / GVL_PROF_CL_LOSS_BWD
  * 19: + gvl_beam_step_f32 / gvl_beam_finish_f32 (beam-search decoding of the captioner: per token the top W of W * V continuation
  *      scores with finished-beam handling and the re-ordering of the recurrent state by parent beam in one launch; the final
  *      ranking and back-trace); profiling tags GVL_PROF_BEAM / GVL_PROF_BEAM_FINISH
@@ -543,6 +546,9 @@ int gvl_ce_rows_backward_f32(float *logits, int64_t ld, int R, int V, const int6
 #define GVL_PROF_MHA_TRAIN 25
 #define GVL_PROF_BEAM 26
 #define GVL_PROF_BEAM_FINISH 27
+#define GVL_PROF_CL_LOGITS 28
+#define GVL_PROF_CL_LOSS_FWD 29
+#define GVL_PROF_CL_LOSS_BWD 30
 int gvl_prof_enable(int on);   /* 0 off | 1 sampling-path kernels | 2 also GVL_PROF_PROJ (stamping two consecutive launches
                                   inflates the second one's interval by 2-3 us, so level 1 leaves the projection alone) */
 /* Phase stamps of the temporal kernels (diagnostics): while a DEVICE buffer of 2 x 4096 x 4 uint64 is set, every
@@ -823,6 +829,42 @@ int gvl_hungarian_batch_f32(const float *C, int B, int Q, int G, const int *size
  *   max_rows / max_cols: the largest min(Q, n*tile) and max(Q, n*tile) over the problems (<= 256 / <= 1024). */
 int gvl_lsap_batch_device_f32(const float *C, const int64_t *problems, int n_problems, int max_rows, int max_cols,
                               int64_t *rows_out, int64_t *cols_out, int *status, void *stream);
+
+/* -- the contrastive event-text branch (ABI 20; gvl_contrastive.hip).  fp32, plain FMAs, no float atomics: bitwise repeatable.
+ *    Sizes: L decoder layers, E = B Q event rows, G text rows (1 <= G <= 4096), 1 <= D <= 512.
+ *
+ *    gvl_cl_logits_f32 -- ContrastiveCriterion.forward_logits(text, event, bg).t() (pdvc/criterion.py:281-288, transposed as
+ *    pdvc/pdvc.py:488 does) for all layers:  out (L, E, G [+ 1]),  out[l][e][g] = <e_le / max(|e_le|, 1e-12), t_lg / max(|t_lg|, 1e-12)>,
+ *    column G the same with bg (D; NULL = no such column).  event (L, E, D); text: layer l at text + l * text_layer_stride floats
+ *    (0 = one tensor for all layers), (G, D).  inv_e (L, E), inv_t (L, G), inv_bg (1): the inverse clamped norms, for the backward.
+ *
+ *    gvl_cl_loss_forward_f32 -- ContrastiveCriterion.forward (criterion.py:291-348) on those logits.  Matched pairs of layer l:
+ *    p = 0 .. P - 1, text row pair_t[l][p] + pair_tbase[p] (pair_tbase may be NULL), event row pair_vid[p] Q + pair_q[l][p].
+ *    loss (L, 3) = {loss, t2e, e2t}: t2e the cross-entropy of every matched text over all E events (cross_video) or over its own
+ *    video's Q events, averaged per video and then over the B videos; e2t (needs has_bg and cross_video) per event over the matched
+ *    texts and the background column, averaged over all events (bg_for_cl) or over the matched ones; loss = t2e or their mean.
+ *    Online maximum / sum of exponentials throughout.  Saved for the backward: lse_t (L, G), lse_e (L, E), ev_of_col (L, G),
+ *    col_of_ev (L, E), vid_of_col (L, G) (ints, -1 = none), wcol (L, G), wev (L, E) (the weight of every row's cross-entropy in the
+ *    loss).  workspace: gvl_cl_loss_workspace_bytes(L, E, G) bytes whose first 16 ceil(L / 4) bytes are ZERO on entry.
+ *
+ *    gvl_cl_loss_backward_f32 -- from grad_loss (L), the logits and what the forward saved: the gradients of the UN-normalised event
+ *    rows grad_event (L, E, D), text rows grad_text ((L or 1), G, D: one slab, the sum over the layers in the order l = 0, 1, ..,
+ *    when text_layer_stride == 0) and background row grad_bg (D; sum over the layers), through the temperature, the softmaxes and
+ *    the normalisation  dx = inv (dxh - xh <xh, dxh>)  (a clamped norm is a constant divisor: dx = 1e12 dxh).  Every output row is
+ *    written by the one workgroup that owns it. */
+int gvl_cl_logits_f32(const float *event, const float *text, int64_t text_layer_stride, const float *bg, int L, int E, int G, int D,
+                      float *out, float *inv_e, float *inv_t, float *inv_bg, void *stream);
+size_t gvl_cl_loss_workspace_bytes(int L, int E, int G);
+int gvl_cl_loss_forward_f32(const float *logits, const int64_t *pair_q, const int64_t *pair_t, const int64_t *pair_vid,
+                            const int64_t *pair_tbase, int L, int E, int G, int has_bg, int P, int B, int Q, float temperature,
+                            int cross_video, int e2t, int bg_for_cl, float *loss, float *lse_t, float *lse_e, int *ev_of_col,
+                            int *col_of_ev, int *vid_of_col, float *wcol, float *wev, void *workspace, size_t workspace_bytes,
+                            void *stream);
+int gvl_cl_loss_backward_f32(const float *grad_loss, const float *logits, const float *lse_t, const float *lse_e, const int *ev_of_col,
+                             const int *col_of_ev, const int *vid_of_col, const float *wcol, const float *wev, const float *event,
+                             const float *text, int64_t text_layer_stride, const float *bg, const float *inv_e, const float *inv_t,
+                             const float *inv_bg, int L, int E, int G, int D, int Q, float temperature, float *grad_event,
+                             float *grad_text, float *grad_bg, void *stream);
 
 /* -- TRAINING (ABI 15): the compact (query, caption) pair rows of the captioner on padded targets -- what pdvc.py:540-573 gathers
  *    per decoder layer (matched queries' hidden states, their captions and masks), for the fixed-capacity layout of
