@@ -562,7 +562,10 @@ __global__ void __launch_bounds__(256) k_mha_delta(const float *__restrict__ dou
 int check(const char *what, const float *qkv, int64_t ld, int B, int Q, int H, float p) {
   if (B <= 0 || Q <= 0 || H <= 0 || ld < 3 * H * kD || (ld & 3) || ((uintptr_t)qkv & 15))
     return fail(GVL_EINVAL, "%s: needs B, Q, H > 0, ld >= 3 H 64, ld %% 4 == 0, 16-byte aligned rows", what);
-  if (!(p >= 0.f && p < 1.f)) return fail(GVL_EINVAL, "%s: dropout probability must be in [0, 1) (got %g)", what, (double)p);
+  // p <= 15/16: the P operand of O^T += V^T Pd^T and of dV^T += dO^T Pd is fp16(pd 2^11) with pd <= 1 / (1 - p) -- 2^15 at the
+  // limit (a row with a single valid key has probability exactly 1), infinity in fp16 from p = 0.96874 upward
+  if (!(p >= 0.f && p <= 0.9375f))
+    return fail(GVL_EINVAL, "%s: dropout probability must be in [0, 0.9375] (got %g)", what, (double)p);
   if ((int64_t)B * H * Q * Q >= ((int64_t)1 << 32)) return fail(GVL_EINVAL, "%s: B H Q^2 must stay below 2^32", what);
   return 0;
 }

@@ -151,10 +151,17 @@ class _InProjShared(torch.autograd.Function):
         return dxv + dxq, dxq, gw, gb, None, None
 
 
+MAX_DROPOUT = 0.9375      # check() of gvl_mha_train.hip: the kept weights, at most 1 / (1 - p), enter their products as fp16(2^11 pd)
+
+
 class _Core(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, am, keep, B, Q, H, p, seed, step):
         R = B * Q
+        # (the backward writes a dense dqkv at qkv's leading dimension: a column slice of a wider buffer has no such gradient)
+        if qkv.dim() != 2 or tuple(qkv.shape) != (R, 3 * H * 64) or qkv.stride(1) != 1 or qkv.stride(0) != 3 * H * 64:
+            raise ValueError(f"qkv must be a dense (B Q, 3 H 64) = ({R}, {3 * H * 64}) matrix, got shape {tuple(qkv.shape)} with "
+                             f"strides {tuple(qkv.stride())}")
         out = torch.empty(R, H * 64, device=qkv.device, dtype=torch.float32)
         lse = torch.empty(B, H, Q, device=qkv.device, dtype=torch.float32)
         am_o = TL.step_zeros(R, qkv.device)                     # max |out row|: the row scale of the out-projection behind it
@@ -200,6 +207,7 @@ def eligible(mha, tgt, query_pos):
             and tgt.dim() == 3 and C == mha.embed_dim and C // mha.num_heads == 64 and C % 64 == 0
             and tgt.shape[0] * tgt.shape[1] >= GL.MIN_TRAIN_ROWS and tgt.shape[1] <= 4096
             and tgt.shape[0] * mha.num_heads * tgt.shape[1] * tgt.shape[1] < 2 ** 32
+            and (mha.dropout if mha.training else 0.0) <= MAX_DROPOUT
             and query_pos is not None and query_pos.dim() == 3 and query_pos.shape == tgt.shape and query_pos.stride(0) == 0
             and query_pos.stride(2) == 1 and query_pos.stride(1) % 4 == 0 and query_pos.data_ptr() % 16 == 0
             and query_pos.dtype == torch.float32)

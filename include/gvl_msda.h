@@ -954,8 +954,17 @@ int gvl_planes_refresh_f16(const gvl_plane_desc *descs_device, const int *chunk_
  *    lse (B, H, Q) = log sum_k exp(score) (kept for the backward), dqkv laid out like qkv.  amax_qk / amax_v (B Q): upper bounds of
  *    |row| of the q and k columns / of the v columns (the in-projection's epilogue leaves them).  Dropout: weight (b, h, q, k) is
  *    kept iff hash32(((b H + h) Q + q) Q + k ^ hash32(seed + *step 0x9E3779B9)) >= p 2^32 (the rule of gvl_residual_dropout_*;
- *    the backward is given the step value the forward used); p == 0: plain softmax attention.  A query whose keys are all
- *    excluded yields NaN, as torch.softmax of a fully masked row.  delta_ws (B H Q) and amax_dout_ws (B Q): scratch.
+ *    the backward is given the step value the forward used); p == 0: plain softmax attention; 0 <= p <= 0.9375 (the kept weights,
+ *    at most 1 / (1 - p) = 16, enter their products as fp16 of 2^11 times their value: a larger p is refused).  Within a video the
+ *    elements of q | k (of v) may lie up to 2^13 below that video's largest and keep fp32-level accuracy (an element 2^-k below it
+ *    keeps max(2^-23, 2^(k - 36)) of itself); the videos' ranges are independent.  That holds while the scores are ordinary: the
+ *    backward recomputes P = exp(score - lse) from two fp32 numbers (a relative error of |score| 2^-23), and dq, dk are sums over
+ *    dS = P (dP - delta), a difference of two terms that each carry 2^-22 of sum_c |dO_c| |v_c| -- pure rounding where one key
+ *    carries a query outright (P = 1: dP = delta).  A WHOLE row at 2^10 times the others is outside it: its score with its own key
+ *    is 2^20 times the ordinary ones (2000 and more), and measured there were 6.5e-4 of dk's largest entry (that rounding times a
+ *    q row at 2^10) and 1.4e-5 of dv's; an outlier row in q and v, or in k and v, alone stays at fp32 level.
+ *    A query whose keys are all excluded yields NaN, as torch.softmax of a fully masked row.  delta_ws (B H Q) and amax_dout_ws
+ *    (B Q): scratch.
  *    Products: three fp16 MFMAs per fp32 product in one fp32 accumulator (22-bit operands); scores never leave registers. */
 int gvl_mha_train_forward_f32(const float *qkv, int64_t ld, const unsigned char *key_keep, const float *amax_qk, const float *amax_v,
                               int B, int Q, int H, float p, uint32_t seed, const int64_t *step, float *out, float *lse,

@@ -6,25 +6,10 @@ attention UNDER THAT MASK."""
 import pytest
 import torch
 
+from mha_ref import _hash32, _keep_mask          # noqa: F401  (the mask rule of include/gvl_msda.h, recomputed)
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _hash32(x):
-    m = 0xFFFFFFFF
-    x = x & m
-    x = x ^ (x >> 16); x = (x * 0x7feb352d) & m
-    x = x ^ (x >> 15); x = (x * 0x846ca68b) & m
-    return x ^ (x >> 16)
-
-
-def _keep_mask(B, H, Q, p, seed, step):
-    key = _hash32(torch.tensor((seed + step * 0x9E3779B9) & 0xFFFFFFFF, dtype=torch.int64, device=DEV))
-    idx = torch.arange(B * H * Q * Q, dtype=torch.int64, device=DEV)
-    # (the kernel receives p as a C float: 0.1f 2^32 is 7 above 0.1 2^32 -- one mask element in 6e8 would differ, which fails
-    #  this test at about one (seed, step) pair in fifty)
-    thr = min(int(float(torch.tensor(p, dtype=torch.float32)) * 4294967296.0), 0xFFFFFFFF)
-    return (_hash32(idx ^ key) >= thr).view(B, H, Q, Q)
 
 
 def _ref_attention(x, pos, w, b, wo, bo, H, key_keep, drop_keep, p):
