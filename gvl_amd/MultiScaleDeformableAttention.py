@@ -917,7 +917,7 @@ PROF_TAGS = {1: "fwd_t1d_d64", 2: "fwd_generic", 3: "bwd_t1d_d64", 4: "bwd_gener
              12: "cap_train_fwd", 13: "cap_train_bwd", 14: "lstm_train", 15: "match_cost", 16: "criterion",
              17: "pos_embed", 18: "col_sum", 19: "proj", 20: "split_rows", 21: "gemm_f16x3", 22: "layer_gemm",
              23: "layer_norm_etc", 24: "wgrad_f16x3", 25: "mha_train", 26: "beam_step", 27: "beam_finish",
-             28: "cl_logits", 29: "cl_loss_fwd", 30: "cl_loss_bwd"}
+             28: "cl_logits", 29: "cl_loss_fwd", 30: "cl_loss_bwd", 31: "capt_embed", 32: "capt_attend"}
 
 
 def clock_probe_mhz(device=None, n_fma=20000):

@@ -6,7 +6,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GVL_LIB_PATH: a dev build (gvl_amd.build.build_dev: timing / ablation variants of single kernels) instead of the shipped library
 LIB_PATH = os.environ.get("GVL_LIB_PATH") or os.path.join(_HERE, "libgvl_msda.so")
-ABI_VERSION = 20          # include/gvl_msda.h GVL_MSDA_ABI_VERSION
+ABI_VERSION = 21          # include/gvl_msda.h GVL_MSDA_ABI_VERSION
 _lock = threading.Lock()
 _lib = None
 
@@ -149,6 +149,9 @@ SIGNATURES = {
     "gvl_cl_loss_workspace_bytes": (_SZ, [_I, _I, _I]),
     "gvl_cl_loss_forward_f32": (_I, [_P] * 5 + [_I] * 7 + [ctypes.c_float] + [_I] * 3 + [_P] * 9 + [_SZ, _P]),
     "gvl_cl_loss_backward_f32": (_I, [_P] * 10 + [_P, _I64] + [_P] * 4 + [_I] * 5 + [ctypes.c_float] + [_P] * 4),
+    "gvl_capt_embed_f32": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "gvl_capt_attend_applicable": (_I, [_I, _I, _I]),
+    "gvl_capt_attend_f32": (_I, [_P, _I64, _P, _I64, _P, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _P, _P]),
 }
 
 

@@ -3,7 +3,8 @@
 Mirrors pdvc/pdvc.py:41-314 (model + forward), :434-519 (eval: parallel_prediction_full), :540-660 (train:
 parallel_prediction_matched), :699-884 (caption_prediction / caption_prediction_eval) and :1181-1238 (build), for the
 configuration space of BASELINE.json: ``transformer_input_type='queries'``, LSTM-DSA captioner
-(``caption_decoder_type: standard``).  ``enable_contrastive=True`` builds the contrastive event-text branch of the ``*_ssvg``
+(``caption_decoder_type: standard``); the Transformer-DSA captioner (``transformer``) is built too and takes the per-layer
+caption path.  ``enable_contrastive=True`` builds the contrastive event-text branch of the ``*_ssvg``
 configurations (pdvc.py:62-109,148-165,211-248: word-level pool, the two projections, the background embedding, the cosine
 logits in the matcher cost, the InfoNCE losses) around a FROZEN text encoder that the caller passes in -- any module with the
 encoder's interface, e.g. ``gvl_amd.text.PrecomputedTextEncoder`` over pre-extracted features; no weights are downloaded and
@@ -639,12 +640,12 @@ class PDVC(nn.Module):
         return out, loss
 
     def caption_prediction_eval(self, cap_head, dt, hs, reference, others, decoder_type, indices=None):
-        """pdvc.py:885-930 for the 'none' and 'standard' heads."""
+        """pdvc.py:885-930 for the 'none', 'standard' and 'transformer' heads."""
         assert indices is None
         N_, N_q, C = hs.shape
         if decoder_type == 'none':
             return self._no_caption(hs)
-        if decoder_type != 'standard':
+        if decoder_type not in ('standard', 'transformer'):
             raise ValueError(f"caption_decoder_type {decoder_type!r} is not built by gvl_amd")
         with torch.no_grad():
             # beam_size: read AND honoured (the reference reads it at LSTM_DSA.py:132 and decodes greedily); 1 = the greedy path
@@ -854,7 +855,7 @@ class PDVC(nn.Module):
         return unbind_tagged(per_layer), {}, dt['cap_tensor'][matches[-1].t_global]
 
     def caption_prediction(self, cap_head, dt, hs, reference, others, indices):
-        """Teacher-forced caption loss on the matched (query, caption) pairs (pdvc.py:743-884, 'standard' head):
+        """Teacher-forced caption loss on the matched (query, caption) pairs (pdvc.py:743-884, 'standard' and 'transformer' heads):
         per video the matched queries are packed to the front of a (N, max_pairs, .) tensor, padded rows carry an
         all-False mask and contribute 0 to the mean exactly as in the reference."""
         N_, N_q, C = hs.shape

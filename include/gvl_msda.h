@@ -48,8 +48,11 @@
 extern "C" {
 #endif
 
-#define GVL_MSDA_ABI_VERSION 20
+#define GVL_MSDA_ABI_VERSION 21
 /* ABI history (newest first):
+ * 21: + gvl_capt_embed_f32 / gvl_capt_attend_f32 / gvl_capt_attend_applicable (greedy decoding of the Transformer-DSA caption head
+ *      over a KV cache: the token's embedding row, and causal self-attention of the new position + residual + norm1 in one launch);
+ *      profiling tags GVL_PROF_CAPT_EMBED / GVL_PROF_CAPT_ATTEND
  * 20: + gvl_cl_logits_f32 / gvl_cl_loss_forward_f32 / gvl_cl_loss_backward_f32 / gvl_cl_loss_workspace_bytes (the contrastive
  *      event-text branch: cosine logits of all decoder layers, the InfoNCE losses and their gradient, one launch each);
  *      profiling tags GVL_PROF_CL_LOGITS / GVL_PROF_CL_LOSS_FWD / GVL_PROF_CL_LOSS_BWD
@@ -549,6 +552,8 @@ int gvl_ce_rows_backward_f32(float *logits, int64_t ld, int R, int V, const int6
 #define GVL_PROF_CL_LOGITS 28
 #define GVL_PROF_CL_LOSS_FWD 29
 #define GVL_PROF_CL_LOSS_BWD 30
+#define GVL_PROF_CAPT_EMBED 31
+#define GVL_PROF_CAPT_ATTEND 32
 int gvl_prof_enable(int on);   /* 0 off | 1 sampling-path kernels | 2 also GVL_PROF_PROJ (stamping two consecutive launches
                                   inflates the second one's interval by 2-3 us, so level 1 leaves the projection alone) */
 /* Phase stamps of the temporal kernels (diagnostics): while a DEVICE buffer of 2 x 4096 x 4 uint64 is set, every
@@ -1035,6 +1040,27 @@ int gvl_clip_adam_step_f32(const gvl_adam_desc *descs_device, int n_tensors, con
 int gvl_clip_adam_groups_step_f32(const gvl_adam_desc *descs_device, int n_tensors, const int *chunk_map_device, int n_chunks,
                                   float *partial_device, float *scal_device, float *corr_device, const double *hyper_device,
                                   int n_groups, double max_norm, void *stream);
+
+/* -- greedy decoding of the Transformer-DSA caption head over a KV cache (gvl_cap_tr.hip).  The reference keeps no cache: for each
+ *    token it runs the whole prefix through every layer again (pdvc/CaptioningHead/Transformer_DSA.py:226-238); the head is strictly
+ *    causal, so one new position per row and layer is the same arithmetic.
+ *    gvl_capt_embed_f32: the input row of token step t (Transformer_DSA.py:201-206):
+ *        x[r] = embed[it[r]] + pos_table[t]   (t >= pos_rows: the embedding alone -- rows beyond the table stay zero, :203-205)
+ *      embed (n_vocab, C), pos_table (pos_rows, C), it (n) int64 (ids outside the table are clamped into it), C % 4 == 0 ->
+ *      x (n, C) and amax[r] = max |x[r][.]|, the row scale gvl_linear_f16x3_f32 reads.
+ *    gvl_capt_attend_f32: BertSelfAttention of position t, the residual and norm1 (Transformer_DSA.py:95-99) for n rows:
+ *        cache[0][r][t] = k_t[r];  cache[1][r][t] = v_t[r];
+ *        ctx_h = softmax_{p <= t}(q_h . K_h[p] / 8) V_h[p];   out[r] = LayerNorm(x[r] + ctx)   (biased variance, eps inside the root)
+ *      qkv (n, ld_qkv) rows [q | k | v] of the new position, each C = 64 H wide; x (n, ld_x) the residual rows; cache
+ *      (2, n, positions, C) fp32 with positions [0, t) filled by the earlier steps -- row t is the ONLY part of it written and nothing
+ *      at or behind t is read; gamma, beta (C); out (n, C); amax_out (n) or NULL receives max |out[r][.]| (a plain store: one
+ *      workgroup owns a row).  Head dimension 64, 1 <= H <= 8, 0 <= t < positions <= 64 (gvl_capt_attend_applicable); one workgroup per
+ *      row, one wavefront per head, K and V in 16-byte loads straight to registers, exact fp32 arithmetic. */
+int gvl_capt_embed_f32(const float *embed, int n_vocab, const float *pos_table, int pos_rows, const int64_t *it, int t, int n,
+                       int C, float *x, float *amax, void *stream);
+int gvl_capt_attend_applicable(int H, int D, int positions);
+int gvl_capt_attend_f32(const float *qkv, int64_t ld_qkv, const float *x, int64_t ld_x, float *cache, int n, int positions, int t,
+                        int H, const float *gamma, const float *beta, float eps, float *out, float *amax_out, void *stream);
 
 #ifdef __cplusplus
 }
