@@ -20,6 +20,9 @@ What is restructured for the GPU (results equal up to fp32 rounding):
   * value_proj(memory) and the event-feature half of dim_project do not depend on the token: once per decode;
   * the loop runs without a per-step device->host read (the reference tests ``unfinished.sum() == 0`` every step, :246); the
     all-finished cut is applied once at the end, as in the LSTM-DSA head.
+  * beam search (beam_size > 1) runs on the same cache without ever re-ordering it by parent beam: every beam appends at its own
+    slot, the kernel that selects the beams re-orders a byte table of lineages (MSDA.beam_step_lineage), and the attention reads each
+    earlier position from the slot the lineage names (attend_step_beam): DESIGN.md section 10.
 The decode's new kernels are gvl_amd/csrc/gvl_cap_tr.hip (embed_step, attend_step below); everything else on the token path is the
 split-fp16 Linear / LayerNorm / deformable-attention launches of gvl_amd/layers.py and the fused vocabulary argmax of the LSTM head.
 Teacher forcing (forward) keeps the self-attention and the dropouts on PyTorch ops: DESIGN.md section 10.
@@ -101,6 +104,58 @@ def attend_step(qkv, x, cache, t, H, weight, bias, eps, want_amax=False):
         _lib.check(rc, "capt_attend")
         return y, am
     y = attend_step_torch(qkv, x, cache, t, H, weight, bias, eps)
+    if want_amax:
+        from .. import layers as L
+        return y, L.row_absmax(y)[0]
+    return y, None
+
+
+def attend_beam_kernel_eligible(qkv, x, cache, lineage, H):
+    """domain of gvl_capt_attend_beam_f32: that of gvl_capt_attend_f32, a contiguous uint8 lineage table and at most 8 beams"""
+    C = x.shape[1]
+    return bool(x.is_cuda and qkv.dtype == x.dtype == cache.dtype == torch.float32 and C % H == 0 and qkv.stride(1) == 1
+                and x.stride(1) == 1 and qkv.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and cache.is_contiguous()
+                and qkv.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and lineage.is_contiguous()
+                and _lib.lib().gvl_capt_attend_beam_applicable(H, C // H, cache.shape[2], lineage.shape[1]))
+
+
+def attend_step_beam_torch(qkv, x, cache, lineage, t, H, weight, bias, eps):
+    """the PyTorch formulation of attend_step_beam, on the same cache: the prefix gathered by lineage, the same single write"""
+    R, C = x.shape
+    n, W, _ = lineage.shape
+    D = C // H
+    q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:3 * C]
+    cache[0, :, t] = k
+    cache[1, :, t] = v
+    slot = (torch.arange(n, device=x.device)[:, None, None] * W + lineage[:, :, :t].long().clamp(max=W - 1)).view(R, t)
+    pos = torch.arange(t, device=x.device)[None].expand(R, t)
+    keys = torch.cat([cache[0][slot, pos], k[:, None]], 1).view(R, t + 1, H, D)
+    vals = torch.cat([cache[1][slot, pos], v[:, None]], 1).view(R, t + 1, H, D)
+    scores = torch.einsum("nhd,nphd->nhp", q.reshape(R, H, D), keys) / math.sqrt(D)
+    ctx = torch.einsum("nhp,nphd->nhd", torch.softmax(scores, -1), vals).reshape(R, C)
+    return F.layer_norm(x + ctx, (C,), weight, bias, eps)
+
+
+def attend_step_beam(qkv, x, cache, lineage, t, H, weight, bias, eps, want_amax=False):
+    """attend_step for beam search: the n W rows are W consecutive beams per event, cache (2, n W, positions, C), lineage
+    (n, W, positions) uint8.  Row (r, j) writes k, v at position t of its own slot r W + j (nothing else of the cache is written) and
+    attends over position p < t of slot r W + lineage[r, j, p] and over its own position t -- the cache is never re-ordered by
+    parent beam, the table is (MSDA.beam_step_lineage).  Nothing at or behind t is read, of the cache or of the table; a byte above
+    W - 1 is read as W - 1.  gvl_capt_attend_beam_f32 where it applies, the PyTorch formulation of the same step otherwise."""
+    R, C = x.shape
+    n, W, P = lineage.shape
+    assert R == n * W and qkv.shape == (R, 3 * C) and cache.shape == (2, R, P, C) and 0 <= t < P and lineage.dtype == torch.uint8
+    if attend_beam_kernel_eligible(qkv, x, cache, lineage, H):
+        y = torch.empty(R, C, device=x.device, dtype=torch.float32)
+        am = torch.empty(R, device=x.device, dtype=torch.float32) if want_amax else None
+        with torch.cuda.device(x.device):
+            rc = _lib.lib().gvl_capt_attend_beam_f32(qkv.data_ptr(), qkv.stride(0), x.data_ptr(), x.stride(0), cache.data_ptr(),
+                                                     lineage.data_ptr(), n, W, P, int(t), H, weight.data_ptr(), bias.data_ptr(),
+                                                     float(eps), y.data_ptr(), am.data_ptr() if am is not None else None,
+                                                     torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "capt_attend_beam")
+        return y, am
+    y = attend_step_beam_torch(qkv, x, cache, lineage, t, H, weight, bias, eps)
     if want_amax:
         from .. import layers as L
         return y, L.row_absmax(y)[0]
@@ -329,6 +384,14 @@ class TransformerDSACaptioner(nn.Module):
             qparts.append(F.linear(hs2, layer.dim_project.weight[:, C:]))
         return values, qparts
 
+    def _attend(self, i, layer, qkv, x, t, st, want_amax=False):
+        """the cached self-attention of a token step: through the beams' lineage table when the state carries one (_beam_device)"""
+        norm = layer.norm1
+        if st.get("lineage") is None:
+            return attend_step(qkv, x, st["cache"][i], t, self.n_heads, norm.weight, norm.bias, norm.eps, want_amax=want_amax)
+        return attend_step_beam(qkv, x, st["cache"][i], st["lineage"], t, self.n_heads, norm.weight, norm.bias, norm.eps,
+                                want_amax=want_amax)
+
     def _layer_step_fast(self, i, layer, x, am, t, st):
         """one position through one layer on the hand-written launches: q | k | v, attention over the cache + residual + norm1,
         dim_project (+ the kept event-feature half), offsets | weights, sampling, output_proj + residual, norm2, FFN"""
@@ -338,8 +401,7 @@ class TransformerDSACaptioner(nn.Module):
         wq = L.cached(sa, "qkv", [(sa.query.weight, sa.query.bias), (sa.key.weight, sa.key.bias), (sa.value.weight, sa.value.bias)])
         qkv = L._new(n, 3 * C, x)
         L.linear(x, wq, [L.seg(wq.starts[j], qkv[:, j * C:(j + 1) * C], am, width=C) for j in range(3)])
-        y1, am1 = attend_step(qkv, x, st["cache"][i], t, self.n_heads, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps,
-                              want_amax=True)
+        y1, am1 = self._attend(i, layer, qkv, x, t, st, want_amax=True)
         w = layer.dim_project.weight
         z, am_z = L._new(n, C, x), arena.take(n)
         L.linear(y1, L.cached(layer, "dp_x", lambda: [(w[:, :C], layer.dim_project.bias)], key_of=(w, layer.dim_project.bias)),
@@ -362,7 +424,7 @@ class TransformerDSACaptioner(nn.Module):
         B, Q = st["B"], st["Q"]
         w_qkv, b_qkv = st["qkv_w"][i]
         qkv = F.linear(x, w_qkv, b_qkv)
-        y1, _ = attend_step(qkv, x, st["cache"][i], t, self.n_heads, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps)
+        y1, _ = self._attend(i, layer, qkv, x, t, st)
         z = F.linear(y1, layer.dim_project.weight[:, :C], layer.dim_project.bias) + st["qparts"][i]
         w_cat, b_cat = att._cat_projection()
         proj = F.linear(z, w_cat, b_cat)
@@ -438,23 +500,123 @@ class TransformerDSACaptioner(nn.Module):
                 logits = F.linear(x, self.logits.weight, self.logits.bias).float().contiguous()
         return seq, seq_lp, alive.view(torch.bool)
 
-    def _decode_graphed(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi):
+    def _beam_device(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi, beam_size, length_penalty):
+        """The whole beam search on the device, no host interaction (DESIGN.md sections 4.3 and 10) -> (tokens (n, W, T), logprobs
+        (n, W, T), scores (n, W), lengths (n, W), alive (T,)) in final rank order, T = max_caption_len.  Capturable in a hipGraph.
+        The W beams of an event are W consecutive rows; the token step is the one of _decode_device on n W rows.  After every
+        token the beams of an event are replaced by children of arbitrary parents, and a child attends over its parent's prefix:
+        the cache is NOT re-ordered for that.  Every row appends at its own slot; the kernel that selects the beams
+        (gvl_beam_step_lineage_f32, one launch per token) re-orders a byte table that names, per beam and position, the slot holding
+        it, and the attention (attend_step_beam) reads through that table -- one table for all layers."""
+        from .. import layers as L
+        W, T, V1 = beam_size, self.max_caption_len, self.vocab_size + 1
+        B, Q, C = hs.shape
+        n, nl, dev = B * Q, len(self.layers), hs.device
+        R = n * W
+        hs = hs.contiguous()
+        fast = self._layers_ok(hs, memory, tshapes)
+        # value_proj(memory) per video, the event-feature half of dim_project per EVENT and repeated over its beams
+        values, qparts = self._decode_constants(hs.view(n, C), memory, mask, fast)
+        qparts = [q_.repeat_interleave(W, 0) for q_ in qparts]
+        # ONE zero fill: the <bos> ids, the `alive` words, the first step's finished flags, the two lineage tables
+        b_l = (8 * R + 15) // 16 * 16
+        raw = torch.zeros(b_l + 4 * T + R + 2 * R * T, dtype=torch.uint8, device=dev)
+        it = raw[:8 * R].view(torch.long)
+        alive = raw[b_l:b_l + 4 * T].view(torch.int32)
+        fin = raw[b_l + 4 * T:b_l + 4 * T + R].view(n, W)
+        lins = raw[b_l + 4 * T + R:].view(2, n, W, T)
+        st = {"B": B, "Q": Q * W, "values": values, "qparts": qparts, "tshapes": tshapes, "lsi": lsi,
+              "ref_in": self._scaled_reference(reference.repeat_interleave(W, 1), {'valid_ratios': valid_ratios}).contiguous(),
+              "shapes2d": temporal_shapes_2d(tshapes, lsi), "host": getattr(tshapes, "_gvl_host_lengths", None),
+              # position p of slot s is written by step p, by the beam that sits at s then, and read through the lineages behind it
+              "cache": torch.empty(nl, 2, R, T, C, device=dev, dtype=torch.float32)}
+        if fast:
+            st["arena"] = L._Arena((3 * T * nl + 2) * (R + 4), dev)
+        else:
+            st["qkv_w"] = self._torch_weights()
+        score = torch.full((n, W), float("-inf"), dtype=torch.float32, device=dev)
+        score[:, 0] = 0.0                                              # beam 0 alone is live: the first step yields W distinct beams
+        scores = (torch.empty_like(score), torch.empty_like(score))
+        fins = (torch.empty_like(fin), torch.empty_like(fin))
+        parents = torch.empty(T, n, W, dtype=torch.int32, device=dev)
+        tokens = torch.empty(T, n, W, dtype=torch.long, device=dev)
+        logps = torch.empty(T, n, W, dtype=torch.float32, device=dev)
+        ld = (V1 + 3) // 4 * 4                                          # rows of the logits padded to 16 bytes
+        logit_buf = torch.empty(R, ld, dtype=torch.float32, device=dev)
+        pos_table = self.pos_table[0]
+        kernel_embed = C % 4 == 0 and self.embed.weight.dtype == torch.float32
+        for t in range(T):
+            st["lineage"] = lins[t & 1]                                 # positions [0, t) of the current beams
+            if kernel_embed:
+                x, am = embed_step(self.embed.weight, pos_table, it, t)
+            else:
+                x, am = self.embed.weight[it] + (pos_table[t] if t < pos_table.shape[0] else 0.0), None
+            if fast and am is None:
+                am, _ = L.row_absmax(x)
+            for i, layer in enumerate(self.layers):
+                if fast:
+                    x, am = self._layer_step_fast(i, layer, x, am, t, st)
+                else:
+                    x = self._layer_step_torch(i, layer, x, t, st)
+            planes = self._logit_planes(x)
+            if planes is not None:                                      # fp32 product on the fp16 matrix cores, logits written
+                logits = MSDA.gemm_f16x3(MSDA.split_rows(x), planes, self.logits.bias, out=logit_buf[:, :V1])
+            else:
+                logits = F.linear(x, self.logits.weight, self.logits.bias).float().contiguous()
+            MSDA.beam_step_lineage(logits, score, fin, lins[t & 1], lins[(t + 1) & 1], t, scores[t & 1], fins[t & 1], parents[t],
+                                   tokens[t], logps[t], alive[t:t + 1])
+            score, fin, it = scores[t & 1], fins[t & 1], tokens[t].view(-1)
+        return MSDA.beam_finish(parents, tokens, logps, score, length_penalty) + (alive != 0,)
+
+    def beam_search(self, hs, reference, others, beam_size, length_penalty=0.0):
+        """Beam-search decoding over the KV cache (semantics: DESIGN.md section 4.3, as LSTM_DSA.Captioner.beam_search) -> dict, every
+        entry in final rank order (rank = score / len ** length_penalty, len = emitted tokens with the end token; the penalty is never
+        applied during the search):
+            tokens (n, W, T) int64 and logprobs (n, W, T), zero behind a beam's end token;  scores (n, W) sum of log-probs;
+            lengths (n, W) tokens in front of the end token;  alive (T,) bool: some beam is still live after token t.
+        No host read in here.  With graph_decode set the loop is replayed from a hipGraph: the outputs are then the graph's static
+        tensors, overwritten by the next call."""
+        W = int(beam_size)
+        if not 1 <= W <= MSDA.BEAM_MAX:
+            raise ValueError(f"beam_size must be 1 .. {MSDA.BEAM_MAX} (got {beam_size})")
+        if W > self.vocab_size + 1:
+            raise ValueError(f"beam_size {W} exceeds the {self.vocab_size + 1} vocabulary entries")
+        if not hs.is_cuda:
+            raise NotImplementedError(f"beam_size > 1: the Transformer-DSA head searches on a ROCm device only (no CPU fallback); "
+                                      f"got {hs.device}")
+        if torch.is_autocast_enabled():
+            raise NotImplementedError("beam search decodes in fp32: the bf16-storage decode under torch.autocast is not built")
+        if torch.is_grad_enabled():
+            raise RuntimeError("beam search is inference only: call it under torch.no_grad()")
+        memory, tshapes, lsi, mask = self._level_inputs(others)
+        args = (hs, reference, memory, mask, others['valid_ratios'], tshapes, lsi)
+        if getattr(self, "graph_decode", False) and getattr(tshapes, "_gvl_host_lengths", None) is not None:
+            out = self._decode_graphed(*args, beam=(W, float(length_penalty)))
+        else:
+            out = self._beam_device(*args, W, float(length_penalty))
+        return dict(zip(("tokens", "logprobs", "scores", "lengths", "alive"), out))
+
+    def _decode_graphed(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi, beam=(1, 0.0)):
         """the greedy loop replayed from a hipGraph, captured once per input shape and parameter version (as
-        LSTM_DSA.Captioner._decode_graphed)"""
+        LSTM_DSA.Captioner._decode_graphed).  beam = (beam_size, length_penalty) with beam_size > 1: the beam search (_beam_device)
+        instead, by the same cache."""
         cache = self.__dict__.get("_decode_graphs")
         if cache is None:
             cache = self.__dict__["_decode_graphs"] = _LRU(16)
         # weight-derived operands (planes, concatenated matrices) are cached per parameter version and become constants of the
         # captured graph: a parameter update must lead to a new capture
         key = (tuple(hs.shape), tuple(reference.shape), tuple(memory.shape), str(hs.device), tuple(tshapes._gvl_host_lengths[0]),
-               mask is not None, sum(p_._version for p_ in self.parameters()))
+               mask is not None, tuple(beam), sum(p_._version for p_ in self.parameters()))
         if cache and next(iter(cache))[-1] != key[-1]:
             cache.clear()                                    # parameters changed: graphs of the old weights are dead
         entry = cache.lookup(key)
         ins = [t_ for t_ in (hs, reference, memory, mask, valid_ratios)]
         if entry is None:
             static = [t_.clone() if t_ is not None else None for t_ in ins]
-            decode = lambda: self._decode_device(*static, tshapes, lsi)      # noqa: E731
+            if beam[0] > 1:
+                decode = lambda: self._beam_device(*static, tshapes, lsi, *beam)      # noqa: E731
+            else:
+                decode = lambda: self._decode_device(*static, tshapes, lsi)      # noqa: E731
             with side_stream(hs.device) as side:                # warm-up off the capture (lazy inits, weight planes)
                 decode()
             with capture_on(side) as graph:
@@ -471,13 +633,25 @@ class TransformerDSACaptioner(nn.Module):
     @_fp32_island
     def sample(self, hs, reference, others, opt={}):
         """Greedy decoding (Transformer_DSA.py:216-254) -> (seq (N_ * N_q, <= max_caption_len), logprobs), or ([], []) when every
-        first token is <end>.  One host read (the `alive` flags), none with defer_trim set (the caller cuts at `last_alive`).  With
+        first token is <end>.  opt['beam_size'] > 1 (with opt['length_penalty'], default 0): the best beam of beam_search in the same
+        form.  One host read (the `alive` flags), none with defer_trim set (the caller cuts at `last_alive`).  With
         graph_decode set the outputs are cut from the graph's static tensors and cloned."""
         if not opt.get('sample_max', 1):
+            if int(opt.get('beam_size', 1) or 1) > 1:
+                raise ValueError("beam_size > 1 needs sample_max = 1: beam search and multinomial sampling exclude each other")
             raise NotImplementedError('Do not support scale logprobs by temperture')            # (the reference's own, :235)
-        if int(opt.get('beam_size', 1) or 1) > 1:
-            raise NotImplementedError("beam_size > 1: beam search is built for caption_decoder_type='standard' only; the "
-                                      "Transformer-DSA head decodes greedily")
+        beam_size = int(opt.get('beam_size', 1) or 1)
+        if beam_size > 1:
+            # the best beam in the greedy branch's form: (n, keep) with keep = the longest returned caption, ([], []) when
+            # every one is empty -- PostProcess reads it as it reads greedy output
+            if getattr(self, "defer_trim", False):
+                raise NotImplementedError("beam search inside a captured whole forward (defer_trim) is not built")
+            with torch.no_grad():
+                res = self.beam_search(hs, reference, others, beam_size, opt.get('length_penalty', 0.0))
+            keep = int(res["lengths"][:, 0].max())                   # the one host read
+            if keep == 0:
+                return [], []
+            return res["tokens"][:, 0, :keep].clone(), res["logprobs"][:, 0, :keep].clone()
         memory, tshapes, lsi, mask = self._level_inputs(others)
         if not hs.is_cuda:
             raise RuntimeError(f"gvl_amd's Transformer-DSA head decodes on a ROCm device only (no CPU fallback); got {hs.device}")

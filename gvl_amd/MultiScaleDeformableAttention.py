@@ -887,6 +887,42 @@ def beam_step(logits, score_in, fin_in, h_in, c_in, score_out, fin_out, parent, 
     _lib.check(rc, "beam_step")
 
 
+LINEAGE_MAX = 64      # include/gvl_msda.h: a lineage table names at most 64 cache positions
+
+
+def beam_step_lineage(logits, score_in, fin_in, lin_in, lin_out, t, score_out, fin_out, parent, token, logp, alive):
+    """beam_step for a decoder that keeps a key / value cache (include/gvl_msda.h: gvl_beam_step_lineage_f32): the same selection,
+    the same records; in place of the state rows it re-orders lin_in (n, W, P) uint8 -- per beam and cache position the slot of
+    the event that holds it -- into lin_out: the parent's bytes in front of position t, the parent itself at t (the position the
+    step just computed), nothing behind t.  At t = 0 nothing of lin_in is read.  The tables may start at any byte."""
+    _require(score_in.dim() == 2, "beam_step_lineage: score_in must be (n, W)")
+    n, W = score_in.shape
+    _require(1 <= W <= BEAM_MAX, f"beam_step_lineage: beam width must be 1 .. {BEAM_MAX} (got {W})")
+    _require(logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == n * W
+             and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1] and logits.shape[1] >= W,
+             "beam_step_lineage: logits must be an (n W, V >= W) fp32 CUDA matrix with unit column stride")
+    V = logits.shape[1]
+    _require(lin_in.dim() == 3 and 1 <= lin_in.shape[2] <= LINEAGE_MAX,
+             f"beam_step_lineage: lin_in must be (n, W, P) with 1 <= P <= {LINEAGE_MAX} cache positions")
+    P = lin_in.shape[2]
+    _require(0 <= int(t) < P, f"beam_step_lineage: the position must be 0 <= t < P = {P} (got {t})")
+    for name, t_, dt, shape in (("score_in", score_in, torch.float32, (n, W)), ("fin_in", fin_in, torch.uint8, (n, W)),
+                                ("score_out", score_out, torch.float32, (n, W)), ("fin_out", fin_out, torch.uint8, (n, W)),
+                                ("parent", parent, torch.int32, (n, W)), ("token", token, torch.int64, (n, W)),
+                                ("logp", logp, torch.float32, (n, W)), ("alive", alive, torch.int32, (1,)),
+                                ("lin_in", lin_in, torch.uint8, (n, W, P)), ("lin_out", lin_out, torch.uint8, (n, W, P))):
+        _require(t_.device == logits.device and t_.dtype == dt and tuple(t_.shape) == shape and t_.is_contiguous(),
+                 f"beam_step_lineage: {name} must be a contiguous {dt} tensor of shape {shape} on the logits' device")
+    for name, a, b in (("lin", lin_in, lin_out), ("score", score_in, score_out), ("fin", fin_in, fin_out)):
+        _require(a.data_ptr() != b.data_ptr(), f"beam_step_lineage: {name}_in and {name}_out ping-pong, nothing is updated in place")
+    with torch.cuda.device(logits.device):
+        rc = _lib.lib().gvl_beam_step_lineage_f32(logits.data_ptr(), logits.stride(0), n, W, V, score_in.data_ptr(),
+                                                  fin_in.data_ptr(), lin_in.data_ptr(), P, int(t), score_out.data_ptr(),
+                                                  fin_out.data_ptr(), parent.data_ptr(), token.data_ptr(), logp.data_ptr(),
+                                                  alive.data_ptr(), lin_out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "beam_step_lineage")
+
+
 def beam_finish(parents, tokens, logps, score, length_penalty=0.0):
     """final ranking and back-trace of a beam search (include/gvl_msda.h: gvl_beam_finish_f32): parents (T, n, W) int32, tokens
     (T, n, W) int64 and logps (T, n, W) as beam_step recorded them, score (n, W) of the last step -> in rank order (score /
@@ -917,7 +953,8 @@ PROF_TAGS = {1: "fwd_t1d_d64", 2: "fwd_generic", 3: "bwd_t1d_d64", 4: "bwd_gener
              12: "cap_train_fwd", 13: "cap_train_bwd", 14: "lstm_train", 15: "match_cost", 16: "criterion",
              17: "pos_embed", 18: "col_sum", 19: "proj", 20: "split_rows", 21: "gemm_f16x3", 22: "layer_gemm",
              23: "layer_norm_etc", 24: "wgrad_f16x3", 25: "mha_train", 26: "beam_step", 27: "beam_finish",
-             28: "cl_logits", 29: "cl_loss_fwd", 30: "cl_loss_bwd", 31: "capt_embed", 32: "capt_attend"}
+             28: "cl_logits", 29: "cl_loss_fwd", 30: "cl_loss_bwd", 31: "capt_embed", 32: "capt_attend",
+             33: "beam_step_lineage", 34: "capt_attend_beam"}
 
 
 def clock_probe_mhz(device=None, n_fma=20000):

@@ -6,7 +6,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GVL_LIB_PATH: a dev build (gvl_amd.build.build_dev: timing / ablation variants of single kernels) instead of the shipped library
 LIB_PATH = os.environ.get("GVL_LIB_PATH") or os.path.join(_HERE, "libgvl_msda.so")
-ABI_VERSION = 21          # include/gvl_msda.h GVL_MSDA_ABI_VERSION
+ABI_VERSION = 22          # include/gvl_msda.h GVL_MSDA_ABI_VERSION
 _lock = threading.Lock()
 _lib = None
 
@@ -89,6 +89,7 @@ SIGNATURES = {
     "gvl_greedy_step_bf16": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "gvl_greedy_step_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "gvl_beam_step_f32": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _I] + [_P] * 9),
+    "gvl_beam_step_lineage_f32": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _I, _I] + [_P] * 8),
     "gvl_beam_finish_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P, _P]),
     "gvl_msda1d_fused_forward_f32": (_I, [_P] * 5 + [_I] * 9 + [_P, _P, _P, _P]),
     "gvl_msda1d_fused_forward_amax_f32": (_I, [_P] * 5 + [_I] * 9 + [_P, _P, _P, _P, _P]),
@@ -152,6 +153,8 @@ SIGNATURES = {
     "gvl_capt_embed_f32": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "gvl_capt_attend_applicable": (_I, [_I, _I, _I]),
     "gvl_capt_attend_f32": (_I, [_P, _I64, _P, _I64, _P, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _P, _P]),
+    "gvl_capt_attend_beam_applicable": (_I, [_I, _I, _I, _I]),
+    "gvl_capt_attend_beam_f32": (_I, [_P, _I64, _P, _I64, _P, _P, _I, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _P, _P]),
 }
 
 

@@ -8,6 +8,9 @@
 //                  arg-max (shuffles inside a wave, LDS across the waves) that leave the beam's W best logits, then the merge of
 //                  the W*W survivors by score and the gather of the W recurrent state rows (h, c) by parent beam.  Correct
 //                  because log_softmax subtracts a per-beam constant: the overall top W lies in the union of every beam's top W.
+//   k_beam_step_lineage  the same selection (one body: beam_select) for the Transformer-DSA head, whose state is a key / value
+//                  cache: instead of gathering state rows it re-orders a byte table of lineages, which the cached attention
+//                  (gvl_cap_tr.hip: k_capt_attend<true>) reads its prefix through.
 //   k_beam_finish  final ranking (score / len^length_penalty) and the back-trace through the recorded parents.
 #include "gvl_common.hpp"
 
@@ -19,6 +22,7 @@ using gvl::fail;
 namespace {
 
 constexpr int kMaxBeam = 8;
+constexpr int kMaxLineage = 64;               // cache positions a lineage table names
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kNoIndex = 0x7fffffff;
@@ -49,21 +53,21 @@ __device__ __forceinline__ void lse_max(float &m, float &s, float mx) {
   }
 }
 
+// The selection of one token step, shared by both kernels below: leaves the step's records in global memory and the parent of every
+// new beam in s_parent (W ints of the caller's LDS), behind a barrier.
 // KW: capacity of the per-thread candidate list, the smallest of 1, 2, 4, 8 that holds the beam width W
 template <int KW>
-__global__ void __launch_bounds__(kThreads)
-k_beam_step(const float *__restrict__ logits, int64_t ld, int V, int W, int H, const float *__restrict__ score_in,
-            const unsigned char *__restrict__ fin_in, const float *__restrict__ h_in, const float *__restrict__ c_in,
-            float *__restrict__ score_out, unsigned char *__restrict__ fin_out, int *__restrict__ parent_out,
-            int64_t *__restrict__ token_out, float *__restrict__ logp_out, int *__restrict__ alive,
-            float *__restrict__ h_out, float *__restrict__ c_out) {
+__device__ __forceinline__ void beam_select(const float *__restrict__ logits, int64_t ld, int V, int W,
+                                            const float *__restrict__ score_in, const unsigned char *__restrict__ fin_in,
+                                            float *__restrict__ score_out, unsigned char *__restrict__ fin_out,
+                                            int *__restrict__ parent_out, int64_t *__restrict__ token_out,
+                                            float *__restrict__ logp_out, int *__restrict__ alive, int *s_parent) {
   __shared__ float s_wm[kWaves], s_ws[kWaves];                 // per-wave max / sum exp
   __shared__ float s_rv[2][kWaves];                            // per-wave winner of an arg-max round (double-buffered)
   __shared__ int s_ri[2][kWaves];
   __shared__ float s_cv[kMaxBeam * kMaxBeam];                  // the W * W survivors: score, token log-prob, flat index
   __shared__ float s_cl[kMaxBeam * kMaxBeam];
   __shared__ int s_ci[kMaxBeam * kMaxBeam];
-  __shared__ int s_parent[kMaxBeam];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float kNegInf = -INFINITY;
   if (tid < W) s_parent[tid] = tid;
@@ -196,6 +200,18 @@ k_beam_step(const float *__restrict__ logits, int64_t ld, int V, int W, int H, c
     }
   }
   __syncthreads();
+}
+
+template <int KW>
+__global__ void __launch_bounds__(kThreads)
+k_beam_step(const float *__restrict__ logits, int64_t ld, int V, int W, int H, const float *__restrict__ score_in,
+            const unsigned char *__restrict__ fin_in, const float *__restrict__ h_in, const float *__restrict__ c_in,
+            float *__restrict__ score_out, unsigned char *__restrict__ fin_out, int *__restrict__ parent_out,
+            int64_t *__restrict__ token_out, float *__restrict__ logp_out, int *__restrict__ alive,
+            float *__restrict__ h_out, float *__restrict__ c_out) {
+  __shared__ int s_parent[kMaxBeam];
+  beam_select<KW>(logits, ld, V, W, score_in, fin_in, score_out, fin_out, parent_out, token_out, logp_out, alive, s_parent);
+  const int row = blockIdx.x, tid = threadIdx.x;
   // the recurrent state of the new beams: rows of this event re-ordered by parent, into the other pair of buffers
   const int h4 = H >> 2;
   for (int i = tid; i < W * h4; i += kThreads) {
@@ -204,6 +220,26 @@ k_beam_step(const float *__restrict__ logits, int64_t ld, int V, int W, int H, c
     reinterpret_cast<float4 *>(h_out)[dst] = reinterpret_cast<const float4 *>(h_in)[src];
     reinterpret_cast<float4 *>(c_out)[dst] = reinterpret_cast<const float4 *>(c_in)[src];
   }
+}
+
+// The same selection for a decoder that keeps a key / value cache instead of a recurrent state: nothing of the cache moves.  Each
+// beam carries a lineage, lin[r][j][q] = the slot (0 .. W-1) of event r that holds position q of beam j's prefix; the new beam j with
+// parent p inherits p's lineage in front of t and names p itself at t, where p's slot has just been written.  Bytes, any alignment.
+template <int KW>
+__global__ void __launch_bounds__(kThreads)
+k_beam_step_lineage(const float *__restrict__ logits, int64_t ld, int V, int W, const float *__restrict__ score_in,
+                    const unsigned char *__restrict__ fin_in, const unsigned char *__restrict__ lin_in, int P, int t,
+                    float *__restrict__ score_out, unsigned char *__restrict__ fin_out, int *__restrict__ parent_out,
+                    int64_t *__restrict__ token_out, float *__restrict__ logp_out, int *__restrict__ alive,
+                    unsigned char *__restrict__ lin_out) {
+  __shared__ int s_parent[kMaxBeam];
+  beam_select<KW>(logits, ld, V, W, score_in, fin_in, score_out, fin_out, parent_out, token_out, logp_out, alive, s_parent);
+  const int row = blockIdx.x, tid = threadIdx.x;
+  for (int i = tid; i < W * t; i += kThreads) {                // (t = 0: nothing of lin_in is read)
+    const int nb = i / t, q = i - nb * t;
+    lin_out[((int64_t)row * W + nb) * P + q] = lin_in[((int64_t)row * W + s_parent[nb]) * P + q];
+  }
+  if (tid < W) lin_out[((int64_t)row * W + tid) * P + t] = (unsigned char)s_parent[tid];
 }
 
 // one thread per (event row, beam); a workgroup holds whole rows
@@ -271,6 +307,28 @@ int gvl_beam_step_f32(const float *logits, int64_t logits_ld, int n, int W, int 
   return gvl::launch(GVL_PROF_BEAM, n, W, "k_beam_step", kern, dim3(n), dim3(kThreads), 0, (hipStream_t)stream, logits,
                      logits_ld, V, W, H, score_in, fin_in, h_in, c_in, score_out, fin_out, parent_out, token_out, logp_out, alive,
                      h_out, c_out);
+}
+
+int gvl_beam_step_lineage_f32(const float *logits, int64_t logits_ld, int n, int W, int V, const float *score_in,
+                              const unsigned char *fin_in, const unsigned char *lin_in, int P, int t, float *score_out,
+                              unsigned char *fin_out, int *parent_out, int64_t *token_out, float *logp_out, int *alive,
+                              unsigned char *lin_out, void *stream) {
+  if (n < 0 || W < 1 || W > kMaxBeam || V < W || logits_ld < V || P < 1 || P > kMaxLineage || t < 0 || t >= P ||
+      (int64_t)W * V > 0x7ffffff0)
+    return fail(GVL_EINVAL, "gvl_beam_step_lineage_f32: bad sizes n=%d W=%d V=%d ld=%lld P=%d t=%d (1 <= W <= %d, W <= V, "
+                "0 <= t < P <= %d)", n, W, V, (long long)logits_ld, P, t, kMaxBeam, kMaxLineage);
+  if (n == 0) return 0;
+  if (!logits || !score_in || !fin_in || !lin_in || !score_out || !fin_out || !parent_out || !token_out || !logp_out || !alive ||
+      !lin_out)
+    return fail(GVL_EINVAL, "gvl_beam_step_lineage_f32: null pointer");
+  if (lin_in == lin_out || score_in == score_out || fin_in == fin_out)
+    return fail(GVL_EINVAL, "gvl_beam_step_lineage_f32: the lineage, score and flag buffers ping-pong, nothing is updated in place");
+  if (reinterpret_cast<uintptr_t>(logits) & 3) return fail(GVL_EINVAL, "gvl_beam_step_lineage_f32: logits must be 4-byte aligned");
+  auto kern = W == 1 ? k_beam_step_lineage<1> : W == 2 ? k_beam_step_lineage<2> : W <= 4 ? k_beam_step_lineage<4>
+                                                                                            : k_beam_step_lineage<8>;
+  return gvl::launch(GVL_PROF_BEAM_LINEAGE, n, W, "k_beam_step_lineage", kern, dim3(n), dim3(kThreads), 0, (hipStream_t)stream,
+                     logits, logits_ld, V, W, score_in, fin_in, lin_in, P, t, score_out, fin_out, parent_out, token_out, logp_out,
+                     alive, lin_out);
 }
 
 int gvl_beam_finish_f32(const int *parents, const int64_t *tokens, const float *logps, const float *score, int n, int W, int T,

@@ -13,6 +13,7 @@
 //                  projection's output row, never read back from the cache; no position behind t is touched.  LayerNorm
 //                  statistics over the H heads go through LDS (two passes: mean, then the centred sum of squares).
 //                  Plain fp32 FMAs: the step is a read of (t + 1) x 2 x 256 bytes per head, the matrix cores have nothing to do.
+//                  k_capt_attend<true> is the same step for beam search: position p < t comes from the slot the row's lineage names.
 #include "gvl_common.hpp"
 
 #include <math.h>
@@ -24,6 +25,7 @@ namespace {
 constexpr int kHeadDim = 64;
 constexpr int kMaxHeads = 8;
 constexpr int kMaxPositions = 64;
+constexpr int kMaxBeam = 8;
 
 __global__ void __launch_bounds__(64)
 k_capt_embed(const float *__restrict__ embed, int n_vocab, const float *__restrict__ pos_table, int pos_rows,
@@ -56,10 +58,16 @@ __device__ __forceinline__ void merge(float &m, float &s, float4 &a, float m2, f
   m = mn;
 }
 
+// kBeam: the rows are n / W events of W beams (beam search, gvl_beam.hip: k_beam_step_lineage).  A row still appends position t at
+// its OWN slot, but reads position p < t from the slot of its event that lineage[row][p] names -- the cache is never copied by
+// parent.  A quarter-wave's sixteen loads are one position of one head, so the slot is one base address per quarter-wave and
+// position; the row's lineage (Tc <= 64 bytes) is fetched once, one byte per lane, and handed out by a shuffle per position.
+template <bool kBeam>
 __global__ void __launch_bounds__(64 * kMaxHeads)
 k_capt_attend(const float *__restrict__ qkv, int64_t ld_qkv, const float *__restrict__ xres, int64_t ld_x,
-              float *__restrict__ cache, int n, int Tc, int t, int H, const float *__restrict__ gamma,
-              const float *__restrict__ beta, float eps, float *__restrict__ out, float *__restrict__ amax_out) {
+              float *__restrict__ cache, const unsigned char *__restrict__ lineage, int W, int n, int Tc, int t, int H,
+              const float *__restrict__ gamma, const float *__restrict__ beta, float eps, float *__restrict__ out,
+              float *__restrict__ amax_out) {
   __shared__ float s_part[kMaxHeads];
   __shared__ float s_part2[kMaxHeads];
   __shared__ float s_max[kMaxHeads];
@@ -77,15 +85,23 @@ k_capt_attend(const float *__restrict__ qkv, int64_t ld_qkv, const float *__rest
     *reinterpret_cast<float4 *>(kc + (int64_t)t * C) = k_new;
     *reinterpret_cast<float4 *>(vc + (int64_t)t * C) = v_new;
   }
+  int slot = 0;                                                                        // lane p: the slot of position p, p < t
+  int64_t to_event = 0;                                                                // from this row's slot to slot 0 of its event
+  if (kBeam) {
+    if (lane < t) slot = min((int)lineage[(int64_t)row * Tc + lane], W - 1);           // (clamped: never an address outside the event)
+    to_event = -(int64_t)(row % W) * Tc * C;
+  }
   float m = -INFINITY, s = 0.f;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int p0 = 0; p0 <= t; p0 += 4) {                                                 // uniform over the wavefront
     const int p = p0 + sub;
     const bool live = p <= t;
     float4 kk = k_new, vv = v_new;
+    int64_t at = (int64_t)p * C;
+    if (kBeam) at += to_event + (int64_t)__shfl(slot, p & 63, 64) * Tc * C;             // (every lane takes part in the shuffle)
     if (p < t) {                                                                       // (p == t: the registers; p > t: unused)
-      kk = *reinterpret_cast<const float4 *>(kc + (int64_t)p * C);
-      vv = *reinterpret_cast<const float4 *>(vc + (int64_t)p * C);
+      kk = *reinterpret_cast<const float4 *>(kc + at);
+      vv = *reinterpret_cast<const float4 *>(vc + at);
     }
     float d = fmaf(q.x, kk.x, fmaf(q.y, kk.y, fmaf(q.z, kk.z, q.w * kk.w)));
 #pragma unroll
@@ -183,8 +199,33 @@ int gvl_capt_attend_f32(const float *qkv, int64_t ld_qkv, const float *x, int64_
   if (!qkv || !x || !cache || !gamma || !beta || !out) return fail(GVL_EINVAL, "gvl_capt_attend_f32: null pointer");
   if (misaligned16(qkv) || misaligned16(x) || misaligned16(cache) || misaligned16(gamma) || misaligned16(beta) || misaligned16(out))
     return fail(GVL_EINVAL, "gvl_capt_attend_f32: every tensor must be 16-byte aligned");
-  return gvl::launch(GVL_PROF_CAPT_ATTEND, n, t, "k_capt_attend", k_capt_attend, dim3(n), dim3(64 * H), 0, (hipStream_t)stream, qkv,
-                     ld_qkv, x, ld_x, cache, n, positions, t, H, gamma, beta, eps, out, amax_out);
+  return gvl::launch(GVL_PROF_CAPT_ATTEND, n, t, "k_capt_attend", k_capt_attend<false>, dim3(n), dim3(64 * H), 0,
+                     (hipStream_t)stream, qkv, ld_qkv, x, ld_x, cache, (const unsigned char *)nullptr, 1, n, positions, t, H, gamma,
+                     beta, eps, out, amax_out);
+}
+
+int gvl_capt_attend_beam_applicable(int H, int D, int positions, int W) {
+  return gvl_capt_attend_applicable(H, D, positions) && W >= 1 && W <= kMaxBeam;
+}
+
+int gvl_capt_attend_beam_f32(const float *qkv, int64_t ld_qkv, const float *x, int64_t ld_x, float *cache,
+                             const unsigned char *lineage, int n, int W, int positions, int t, int H, const float *gamma,
+                             const float *beta, float eps, float *out, float *amax_out, void *stream) {
+  if (!gvl_capt_attend_beam_applicable(H, kHeadDim, positions, W))
+    return fail(GVL_EINVAL, "gvl_capt_attend_beam_f32: serves head dimension 64, 1 <= H <= %d, 1 <= positions <= %d, 1 <= W <= %d "
+                "(got H=%d positions=%d W=%d)", kMaxHeads, kMaxPositions, kMaxBeam, H, positions, W);
+  const int C = H * kHeadDim;
+  if (n < 0 || (int64_t)n * W > 0x7fffffff || t < 0 || t >= positions || ld_qkv < 3 * C || (ld_qkv & 3) || ld_x < C || (ld_x & 3))
+    return fail(GVL_EINVAL, "gvl_capt_attend_beam_f32: bad sizes n=%d W=%d t=%d positions=%d ld_qkv=%lld ld_x=%lld (0 <= t < "
+                "positions, row strides multiples of 4 that hold the row)", n, W, t, positions, (long long)ld_qkv, (long long)ld_x);
+  if (n == 0) return 0;
+  if (!qkv || !x || !cache || !lineage || !gamma || !beta || !out) return fail(GVL_EINVAL, "gvl_capt_attend_beam_f32: null pointer");
+  if (misaligned16(qkv) || misaligned16(x) || misaligned16(cache) || misaligned16(gamma) || misaligned16(beta) || misaligned16(out))
+    return fail(GVL_EINVAL, "gvl_capt_attend_beam_f32: every fp32 tensor must be 16-byte aligned (the lineage bytes need not be)");
+  const int rows = n * W;
+  return gvl::launch(GVL_PROF_CAPT_ATTEND_BEAM, rows, t, "k_capt_attend_beam", k_capt_attend<true>, dim3(rows), dim3(64 * H), 0,
+                     (hipStream_t)stream, qkv, ld_qkv, x, ld_x, cache, lineage, W, rows, positions, t, H, gamma, beta, eps, out,
+                     amax_out);
 }
 
 }  // extern "C"

@@ -48,8 +48,12 @@
 extern "C" {
 #endif
 
-#define GVL_MSDA_ABI_VERSION 21
+#define GVL_MSDA_ABI_VERSION 22
 /* ABI history (newest first):
+ * 22: + gvl_beam_step_lineage_f32 / gvl_capt_attend_beam_f32 / gvl_capt_attend_beam_applicable (beam-search decoding of the
+ *      Transformer-DSA caption head over its KV cache: the selection re-orders a byte table of lineages instead of a recurrent state,
+ *      the cached self-attention reads each earlier position from the slot its lineage names -- the cache is never copied by parent);
+ *      profiling tags GVL_PROF_BEAM_LINEAGE / GVL_PROF_CAPT_ATTEND_BEAM
  * 21: + gvl_capt_embed_f32 / gvl_capt_attend_f32 / gvl_capt_attend_applicable (greedy decoding of the Transformer-DSA caption head
  *      over a KV cache: the token's embedding row, and causal self-attention of the new position + residual + norm1 in one launch);
  *      profiling tags GVL_PROF_CAPT_EMBED / GVL_PROF_CAPT_ATTEND
@@ -554,6 +558,8 @@ int gvl_ce_rows_backward_f32(float *logits, int64_t ld, int R, int V, const int6
 #define GVL_PROF_CL_LOSS_BWD 30
 #define GVL_PROF_CAPT_EMBED 31
 #define GVL_PROF_CAPT_ATTEND 32
+#define GVL_PROF_BEAM_LINEAGE 33
+#define GVL_PROF_CAPT_ATTEND_BEAM 34
 int gvl_prof_enable(int on);   /* 0 off | 1 sampling-path kernels | 2 also GVL_PROF_PROJ (stamping two consecutive launches
                                   inflates the second one's interval by 2-3 us, so level 1 leaves the projection alone) */
 /* Phase stamps of the temporal kernels (diagnostics): while a DEVICE buffer of 2 x 4096 x 4 uint64 is set, every
@@ -779,7 +785,13 @@ int gvl_greedy_step_f32(const float *logits, int R, int V, int first_step, int64
  *    gvl_beam_finish_f32: final ranking and back-trace of T recorded steps.  parents (T, n, W) int, tokens (T, n, W) int64, logps
  *      (T, n, W), score (n, W) of the last step.  rank value = score / len^length_penalty, len = emitted tokens with the end token
  *      (1 .. T); ties to the smaller beam.  In rank order: out_tokens / out_logps (n, W, T) (zero behind the end token), out_scores
- *      (n, W) the plain sums of log-probs, out_lengths (n, W) int64 = tokens in front of the end token. */
+ *      (n, W) the plain sums of log-probs, out_lengths (n, W) int64 = tokens in front of the end token.
+ *    gvl_beam_step_lineage_f32 (ABI 22): gvl_beam_step_f32 -- the same selection code, every argument and result above unchanged --
+ *      for a decoder whose state is a key / value cache of P positions per beam slot.  In place of h / c it re-orders a table of
+ *      lineages: lin_in, lin_out (n, W, P) unsigned bytes, never the same buffer, any alignment, P <= 64; lin[r][j][q] is the slot
+ *      (0 .. W-1) of event r that holds position q of beam j's prefix.  t (0 <= t < P) is the position the step just computed:
+ *        lin_out[r][j][q] = lin_in[r][parent[r, j]][q] for q < t;   lin_out[r][j][t] = parent[r, j];
+ *      bytes behind position t of lin_out are not written, and at t = 0 nothing of lin_in is read. */
 int gvl_beam_step_f32(const float *logits, int64_t logits_ld, int n, int W, int V, const float *score_in,
                       const unsigned char *fin_in, const float *h_in, const float *c_in, int H, float *score_out,
                       unsigned char *fin_out, int *parent_out, int64_t *token_out, float *logp_out, int *alive,
@@ -787,6 +799,10 @@ int gvl_beam_step_f32(const float *logits, int64_t logits_ld, int n, int W, int 
 int gvl_beam_finish_f32(const int *parents, const int64_t *tokens, const float *logps, const float *score, int n, int W, int T,
                         float length_penalty, int64_t *out_tokens, float *out_logps, float *out_scores, int64_t *out_lengths,
                         void *stream);
+int gvl_beam_step_lineage_f32(const float *logits, int64_t logits_ld, int n, int W, int V, const float *score_in,
+                              const unsigned char *fin_in, const unsigned char *lin_in, int P, int t, float *score_out,
+                              unsigned char *fin_out, int *parent_out, int64_t *token_out, float *logp_out, int *alive,
+                              unsigned char *lin_out, void *stream);
 
 /* -- bf16-input twins of the three inference token-step kernels (BASELINE config 4, "CaptioningHead cross-attn, bf16"):
  *    under torch.autocast the GEMMs of the token loop leave the slab, h2att(h), the gate pre-activations, the
@@ -1055,12 +1071,22 @@ int gvl_clip_adam_groups_step_f32(const gvl_adam_desc *descs_device, int n_tenso
  *      (2, n, positions, C) fp32 with positions [0, t) filled by the earlier steps -- row t is the ONLY part of it written and nothing
  *      at or behind t is read; gamma, beta (C); out (n, C); amax_out (n) or NULL receives max |out[r][.]| (a plain store: one
  *      workgroup owns a row).  Head dimension 64, 1 <= H <= 8, 0 <= t < positions <= 64 (gvl_capt_attend_applicable); one workgroup per
- *      row, one wavefront per head, K and V in 16-byte loads straight to registers, exact fp32 arithmetic. */
+ *      row, one wavefront per head, K and V in 16-byte loads straight to registers, exact fp32 arithmetic.
+ *    gvl_capt_attend_beam_f32 (ABI 22): the same step on n W rows, row r W + j = beam j of event r, for beam search
+ *      (gvl_beam_step_lineage_f32).  cache (2, n W, positions, C); lineage (n, W, positions) unsigned bytes, any alignment:
+ *        cache[.][r W + j][t] = k_t, v_t of the row (its OWN slot, the only part of the cache written);
+ *        position p < t is read from slot r W + min(lineage[r][j][p], W - 1);  position t from the projection's row;
+ *      nothing at or behind t is read, of the cache or of the lineage.  Everything else as gvl_capt_attend_f32, and with W = 1 and
+ *      a zero table the outputs are bitwise its outputs.  Additionally 1 <= W <= 8 (gvl_capt_attend_beam_applicable). */
 int gvl_capt_embed_f32(const float *embed, int n_vocab, const float *pos_table, int pos_rows, const int64_t *it, int t, int n,
                        int C, float *x, float *amax, void *stream);
 int gvl_capt_attend_applicable(int H, int D, int positions);
 int gvl_capt_attend_f32(const float *qkv, int64_t ld_qkv, const float *x, int64_t ld_x, float *cache, int n, int positions, int t,
                         int H, const float *gamma, const float *beta, float eps, float *out, float *amax_out, void *stream);
+int gvl_capt_attend_beam_applicable(int H, int D, int positions, int W);
+int gvl_capt_attend_beam_f32(const float *qkv, int64_t ld_qkv, const float *x, int64_t ld_x, float *cache,
+                             const unsigned char *lineage, int n, int W, int positions, int t, int H, const float *gamma,
+                             const float *beta, float eps, float *out, float *amax_out, void *stream);
 
 #ifdef __cplusplus
 }
