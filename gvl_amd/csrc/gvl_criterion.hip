@@ -234,36 +234,35 @@ __global__ void __launch_bounds__(1024) k_criterion_fwd(CritArgs a, CritDims d, 
     s += (1.f - a.ccr[c]) * bce_logits(a.counts[(int64_t)l * d.B * d.Wd + i], t) * counter_coef(c, tgt, a.beta, a.gau_mask);
   }
   const float loss_counter = block_sum(s, red) / (float)(d.B * d.Wd);
-  // ---- matched boxes: L1 and GIoU (criterion.py:103-121) ----------------------------------------------------------
+  // ---- matched boxes, video by video in pair order: L1 and GIoU with the target (criterion.py:103-121) and the IoU among
+  //      the matched predictions of the video (criterion.py:123-130).  Video v is summed by thread v in both layouts, so
+  //      the padded form adds the same numbers in the same order as the compact one: the same bits ----------------------
   float s1 = 0.f, s2 = 0.f;
-  for (int e = threadIdx.x; e < d.T1; e += blockDim.x) {
-    if (!pair_valid(a, e)) continue;
-    const PairBox p = load_pair(a, d, l, e);
-    s1 += fabsf(p.c - p.tc) + fabsf(p.l - p.tl);
-    const float sx0 = p.c - 0.5f * p.l, sx1 = p.c + 0.5f * p.l, tx0 = p.tc - 0.5f * p.tl, tx1 = p.tc + 0.5f * p.tl;
-    const float inter = fmaxf(fminf(sx1, tx1) - fmaxf(sx0, tx0), 0.f);
-    const float uni = (sx1 - sx0) + (tx1 - tx0) - inter;
-    const float area = fmaxf(fmaxf(sx1, tx1) - fminf(sx0, tx0), 0.f);
-    s2 += 1.f - (inter / (uni + kEps) - (area - uni) / (area + kEps));
-  }
-  const float loss_bbox = block_sum(s1, red) / num_boxes;
-  const float loss_giou = block_sum(s2, red) / num_boxes;
-  // ---- self-IoU of the matched predictions of one video (criterion.py:123-130) ------------------------------------
   s = 0.f;
   for (int v = threadIdx.x; v < d.B; v += blockDim.x) {
     const int e0 = (int)a.ent_start[v], e1 = pairs_end(a, v);
-    float acc = 0.f;
+    float l1 = 0.f, gi = 0.f, acc = 0.f;
     for (int i = e0; i < e1; ++i) {
-      const PairBox pi = load_pair(a, d, l, i);
+      const PairBox p = load_pair(a, d, l, i);
+      l1 += fabsf(p.c - p.tc) + fabsf(p.l - p.tl);
+      const float sx0 = p.c - 0.5f * p.l, sx1 = p.c + 0.5f * p.l, tx0 = p.tc - 0.5f * p.tl, tx1 = p.tc + 0.5f * p.tl;
+      const float inter = fmaxf(fminf(sx1, tx1) - fmaxf(sx0, tx0), 0.f);
+      const float uni = (sx1 - sx0) + (tx1 - tx0) - inter;
+      const float area = fmaxf(fmaxf(sx1, tx1) - fminf(sx0, tx0), 0.f);
+      gi += 1.f - (inter / (uni + kEps) - (area - uni) / (area + kEps));
       for (int j = i + 1; j < e1; ++j) {
         const PairBox pj = load_pair(a, d, l, j);
         float g0, g1;
-        acc += iou_grad(pi.c - 0.5f * pi.l, pi.c + 0.5f * pi.l, pj.c - 0.5f * pj.l, pj.c + 0.5f * pj.l, g0, g1);
+        acc += iou_grad(sx0, sx1, pj.c - 0.5f * pj.l, pj.c + 0.5f * pj.l, g0, g1);
       }
     }
+    s1 += l1;
+    s2 += gi;
     const float cnt = (float)(e1 - e0);
-    s += acc / (0.5f * cnt * (cnt - 1.f));                              // 0/0 = nan for a single match, as the reference
+    s += acc / (0.5f * cnt * (cnt - 1.f));                              // 0/0 = nan below two matches, as the reference
   }
+  const float loss_bbox = block_sum(s1, red) / num_boxes;
+  const float loss_giou = block_sum(s2, red) / num_boxes;
   const float loss_self = block_sum(s, red);
   // ---- cardinality error (criterion.py:88-99; logging only) -------------------------------------------------------
   s = 0.f;

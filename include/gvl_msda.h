@@ -161,7 +161,10 @@ int gvl_match_cost_padded_f32(const float *pred_logits, const float *pred_boxes,
  *                                              step refreshes it per replay); NULL = the scalar argument num_boxes
  *    forward : losses (nl, 6) = [loss_ce, loss_counter, loss_bbox, loss_giou, loss_self_iou, cardinality_error]
  *    backward: grad_losses (nl, 6) -> grad_logits, grad_count, grad_boxes (same shapes as the predictions, fully
- *              written), with PyTorch's subgradient conventions. */
+ *              written), with PyTorch's subgradient conventions.
+ *    A video with fewer than two matches makes loss_self_iou NaN (0 / 0, as the reference's), but adds nothing to grad_boxes:
+ *    the three gradients stay finite next to it, as when the term is left out of the weighted sum.  Every pair sum runs
+ *    video by video in pair order, so the padded layout returns the bits of the compact one. */
 int gvl_set_criterion_forward_f32(const float *pred_logits, const float *pred_count, const float *pred_boxes,
                                   const int64_t *match_q, const int64_t *match_t, const int64_t *pair_video,
                                   const int64_t *pair_target_base, const int64_t *video_pair_start,
