@@ -32,8 +32,8 @@ from ..ops.modules import MSDeformAttnCap
 from ..ops.modules.ms_deform_attn import temporal_shapes_2d
 from .. import MultiScaleDeformableAttention as MSDA
 from ..linear import mirror_linear as _mirror_linear, mirror_linear_eligible as _mirror_ok
-from ..graphs import _LRU, capture_on, side_stream
 from ..linear import Linear, split_gemm_enabled, split_linear, vocab_nll, vocab_nll_eligible
+from .decoding import BeamBooks, DecodingHead, _fp32_island, zero_views
 
 
 class ShowAttendTellCore(nn.Module):
@@ -554,25 +554,6 @@ class TeacherForcedLoop(torch.autograd.Function):
                 d_w_hcat, d_b_hcat, d_w_att, g_aw, g_ab, None, None, None, None, None, None)
 
 
-def _fp32_island(fn):
-    """Mixed-precision policy of gvl_amd under torch.autocast(bfloat16) (BASELINE config 4): the transformer runs its
-    GEMMs / deformable attention on bf16 storage, the recurrent captioner stays fp32 -- its token-step kernels
-    (gvl_cap_attend_f32, gvl_lstm_cell_f32, gvl_row_argmax_lse_f32) are fp32, the recurrence feeds its own rounding
-    back 30 times, and greedy argmax over ~8.5k logits flips on bf16 near-ties.  Inputs arriving in bf16 are widened."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapped(self, hs, reference, others, *args, **kwargs):
-        if not torch.is_autocast_enabled():
-            return fn(self, hs, reference, others, *args, **kwargs)
-        others = dict(others)
-        for k in ("memory", "valid_ratios"):
-            others[k] = others[k].float()
-        with torch.autocast("cuda", enabled=False):
-            return fn(self, hs.float(), reference.float(), others, *args, **kwargs)
-    return wrapped
-
-
 class RowLoss:
     """what Captioner.forward(..., nll=(target, mask)) returns instead of log-probs when the loss never needs them"""
     __slots__ = ("row_loss",)
@@ -581,7 +562,9 @@ class RowLoss:
         self.row_loss = row_loss
 
 
-class Captioner(nn.Module):
+class Captioner(DecodingHead):
+    _reference_line = "LSTM_DSA.py:151"
+
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
@@ -607,31 +590,14 @@ class Captioner(nn.Module):
         return (w.new_zeros(self.num_layers, batch_size, self.rnn_size),
                 w.new_zeros(self.num_layers, batch_size, self.rnn_size))
 
+    def _vocab_layer(self):
+        return self.logit
+
     def build_loss(self, input, target, mask):
-        """LSTM_DSA.py:48-52.  The reference multiplies by a materialised one-hot (n, len, vocab+1) tensor and sums the
-        vocabulary axis: a sum of one term and zeros, i.e. exactly the gathered log-prob -- taken directly here."""
+        """LSTM_DSA.py:48-52"""
         if isinstance(input, RowLoss):                                  # forward(..., nll=(target, mask)) already did it
             return input.row_loss
-        max_len = input.shape[1]
-        picked = input.gather(2, target[:, :max_len, None]).squeeze(2)
-        return -(picked * mask[:, :max_len]).sum(1) / (mask.sum(1) + 1e-6)
-
-    def _scaled_reference(self, reference, others):
-        vr = others['valid_ratios']
-        if reference.shape[-1] == 2:
-            return reference[:, :, None] * torch.stack([vr] * 2, -1)[:, None]
-        return reference[:, :, None] * vr[:, None, :, None]
-
-    def _level_inputs(self, others, reference_points):
-        n_levels = self.core.n_levels
-        if n_levels < self.core.opt.num_feature_levels:
-            # (the reference's own branch cannot run on temporal features: LSTM_DSA.py:151 takes torch.prod(dim=1) of the
-            #  1-D (L,) tensor of level lengths and raises IndexError -- verified by running the reference with
-            #  cap_num_feature_levels = 2; there is no behaviour to mirror)
-            raise NotImplementedError("cap_num_feature_levels < num_feature_levels: the reference itself raises on this "
-                                      "branch for temporal features (LSTM_DSA.py:151) and no config uses it")
-        return (others['memory'], others['spatial_shapes'], others['level_start_index'], others['mask_flatten'],
-                reference_points)
+        return self._masked_row_nll(input, target, mask)
 
     def get_logprobs_state(self, it, state, query, reference_points, input_flatten, input_spatial_shapes,
                            input_level_start_index, mask):
@@ -661,7 +627,7 @@ class Captioner(nn.Module):
             vid_num, query_num, _ = hs.shape
             ref_in = self._scaled_reference(reference, others)
             n = vid_num * query_num
-        memory, tshapes, lsi, mask, ref_in = self._level_inputs(others, ref_in)
+        memory, tshapes, lsi, mask = self._level_inputs(others)
         const = self.core.prepare(hs, memory, mask)
         h = c = None                                   # (zero states: built where the step-by-step loop below needs them)
         w_x = const["w_ih_parts"][0] if "w_ih_parts" in const else self.core.rnn.weight_ih_l0[:, :self.input_encoding_size]
@@ -743,20 +709,6 @@ class Captioner(nn.Module):
                 cached = self._emb_gates = (key, F.linear(w_e, w_x if perm is None else w_x[perm]).contiguous())
         return cached[1]
 
-    def _logit_planes(self, out):
-        """fp16 planes of the vocabulary layer's weight (gvl_split_rows_f16), rebuilt when the weight changes; None when
-        the split product does not apply (training / dropout active, autocast, GVL_GEMM=f32)"""
-        w = self.logit.weight
-        if (self.training or torch.is_grad_enabled() or torch.is_autocast_enabled() or out.dtype != torch.float32
-                or hasattr(out, "_gvl_lowp") or not split_gemm_enabled() or not MSDA.split_eligible(w)):
-            return None
-        key = (w.data_ptr(), w._version)
-        cached = getattr(self, "_logit_p", None)
-        if cached is None or cached[0] != key:
-            with torch.no_grad():
-                cached = self._logit_p = (key, MSDA.split_rows(w.detach()))
-        return cached[1]
-
     def _decode_device(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi, sample_max, temperature):
         """The whole decoding loop on the device, no host interaction: -> (seq (n, T), logprob (n, T), alive (T,))
         with T = max_caption_len.  Capturable in a hipGraph."""
@@ -767,16 +719,10 @@ class Captioner(nn.Module):
         emb_gates = self._embedding_gates(const.get("gate_perm"))
         # the recurrent state is fp32, also under autocast; h, c (and the greedy loop's log-prob table) share ONE zero fill
         # ... and so do the greedy loop's integer state (<bos> tokens, the token table) and its `alive` flags: byte ranges of it
-        T_ = T = self.max_caption_len
-        n_f = 2 * n * self.rnn_size + n * T_
-        b_f = (4 * n_f + 15) // 16 * 16
-        b_l = (8 * (n + n * T) + 15) // 16 * 16
-        raw = torch.zeros(b_f + b_l + T, dtype=torch.uint8, device=hs.device)
-        zbuf = raw[:4 * n_f].view(torch.float32)
-        longs = raw[b_f:b_f + 8 * (n + n * T)].view(torch.long)
-        h = zbuf[:n * self.rnn_size].view(n, self.rnn_size)
-        c = zbuf[n * self.rnn_size:2 * n * self.rnn_size].view(n, self.rnn_size)
-        it = longs[:n]                                                                # <bos>
+        T = self.max_caption_len
+        h, c, seq_lp, it, seq, alive = zero_views(
+            hs.device, (torch.float32, (n, self.rnn_size)), (torch.float32, (n, self.rnn_size)), (torch.float32, (n, T)),
+            (torch.long, (n,)), (torch.long, (n, T)), (torch.uint8, (T,)))                # (it: <bos>)
         if sample_max:
             # greedy: argmax, log-prob and the per-step bookkeeping (unfinished / alive / seq / seq_lp) are one kernel.
             # seq starts as zeros: a loop that is cut short (decode_stop / decode_continue below) leaves exactly what
@@ -784,10 +730,9 @@ class Captioner(nn.Module):
             st = {"hs": hs, "ref_in": ref_in, "tshapes": tshapes, "lsi": lsi, "const": const, "emb_gates": emb_gates,
                   "h": h, "c": c, "it": it, "logits": None,
                   "unfinished": torch.empty(n, dtype=torch.uint8, device=hs.device),
-                  "seq": longs[n:].view(n, T),
-                  "seq_lp": zbuf[2 * n * self.rnn_size:].view(n, T),
+                  "seq": seq, "seq_lp": seq_lp,
                   # alive[t]: some row is still unfinished after token t -- set by the greedy kernel itself
-                  "alive": raw[b_f + b_l:]}
+                  "alive": alive}
             # (running the vocabulary GEMM + argmax of token t on a second stream beside the token-independent half of
             #  step t+1 was tried -- fork / join inside the captured graph -- and measured no gain: 742-757 vs 750
             #  videos/s; the GEMMs already occupy every CU)
@@ -865,63 +810,23 @@ class Captioner(nn.Module):
         ref_in = self._scaled_reference(reference.repeat_interleave(W, 1), {'valid_ratios': valid_ratios})
         const = self.core.prepare(hs, memory, mask)
         emb_gates = self._embedding_gates(const.get("gate_perm"))
-        # one zero fill: h = c = 0, the <bos> ids, the first step's finished flags and the per-step `alive` words
-        n_f = 2 * R * H
-        b_l = (8 * R + 15) // 16 * 16
-        raw = torch.zeros(4 * n_f + b_l + 4 * T + R, dtype=torch.uint8, device=dev)
-        h = raw[:4 * R * H].view(torch.float32).view(R, H)
-        c = raw[4 * R * H:4 * n_f].view(torch.float32).view(R, H)
-        it = raw[4 * n_f:4 * n_f + 8 * R].view(torch.long)
-        alive = raw[4 * n_f + b_l:4 * n_f + b_l + 4 * T].view(torch.int32)
-        fin = raw[4 * n_f + b_l + 4 * T:].view(n, W)
-        score = torch.full((n, W), float("-inf"), dtype=torch.float32, device=dev)
-        score[:, 0] = 0.0                                              # beam 0 alone is live: the first step yields W distinct beams
-        scores = (torch.empty_like(score), torch.empty_like(score))
-        fins = (torch.empty_like(fin), torch.empty_like(fin))
+        # one zero fill: h = c = 0, the <bos> ids, the per-step `alive` words and the first step's finished flags
+        h, c, it, alive, fin = zero_views(dev, (torch.float32, (R, H)), (torch.float32, (R, H)), (torch.long, (R,)),
+                                          (torch.int32, (T,)), (torch.uint8, (n, W)))
+        books = BeamBooks(n, W, T, V1, fin, alive, dev)
         states = ((torch.empty_like(h), torch.empty_like(c)), (torch.empty_like(h), torch.empty_like(c)))
-        parents = torch.empty(T, n, W, dtype=torch.int32, device=dev)
-        tokens = torch.empty(T, n, W, dtype=torch.long, device=dev)
-        logps = torch.empty(T, n, W, dtype=torch.float32, device=dev)
-        ld = (V1 + 3) // 4 * 4                                          # rows of the logits padded to 16 bytes
-        logit_buf = torch.empty(R, ld, dtype=torch.float32, device=dev)
-        for t in range(T):
+        for t, (ins, outs, it_next) in enumerate(books.steps):
             out, (h, c) = self.core.step((emb_gates, it), (h, c), hs, ref_in, tshapes, lsi, const)
             planes = self._logit_planes(out)
             if planes is not None:                                      # fp32 product on the fp16 matrix cores
                 hp = getattr(out, "_gvl_planes", None)
                 logits = MSDA.gemm_f16x3(hp if hp is not None else MSDA.split_rows(out), planes, self.logit.bias,
-                                         out=logit_buf[:, :V1])
+                                         out=books.logits_out)
             else:
                 logits = self.logit(self.dropout(out)).float().contiguous()
-            MSDA.beam_step(logits, score, fin, h, c, scores[t & 1], fins[t & 1], parents[t], tokens[t], logps[t],
-                           alive[t:t + 1], *states[t & 1])
-            score, fin, (h, c), it = scores[t & 1], fins[t & 1], states[t & 1], tokens[t].view(-1)
-        return MSDA.beam_finish(parents, tokens, logps, score, length_penalty) + (alive.view(T) != 0,)
-
-    def beam_search(self, hs, reference, others, beam_size, length_penalty=0.0):
-        """Beam-search decoding (the `beam_size` option the reference reads at LSTM_DSA.py:132 and drops; semantics: DESIGN.md
-        section 4.3) -> dict, every entry in final rank order (rank = score / len ** length_penalty, len = emitted tokens with
-        the end token; the penalty is never applied during the search):
-            tokens (n, W, T) int64 and logprobs (n, W, T), zero behind a beam's end token;  scores (n, W) sum of log-probs;
-            lengths (n, W) tokens in front of the end token;  alive (T,) bool: some beam is still live after token t.
-        No host read in here.  With graph_decode set the loop is replayed from a hipGraph: the outputs are then the graph's static
-        tensors, overwritten by the next call."""
-        W = int(beam_size)
-        if not 1 <= W <= MSDA.BEAM_MAX:
-            raise ValueError(f"beam_size must be 1 .. {MSDA.BEAM_MAX} (got {beam_size})")
-        if W > self.vocab_size + 1:
-            raise ValueError(f"beam_size {W} exceeds the {self.vocab_size + 1} vocabulary entries")
-        if torch.is_autocast_enabled():
-            raise NotImplementedError("beam search decodes in fp32: the bf16-storage decode under torch.autocast is not built")
-        if torch.is_grad_enabled():
-            raise RuntimeError("beam search is inference only: call it under torch.no_grad()")
-        memory, tshapes, lsi, mask, _ = self._level_inputs(others, reference)
-        args = (hs, reference, memory, mask, others['valid_ratios'], tshapes, lsi)
-        if getattr(self, "graph_decode", False) and getattr(tshapes, "_gvl_host_lengths", None) is not None:
-            out = self._decode_graphed(*args, beam=(W, float(length_penalty)))
-        else:
-            out = self._beam_device(*args, W, float(length_penalty))
-        return dict(zip(("tokens", "logprobs", "scores", "lengths", "alive"), out))
+            MSDA.beam_step(logits, *ins, h, c, *outs, *states[t & 1])
+            (h, c), it = states[t & 1], it_next
+        return books.finish(length_penalty)
 
     def decode_continue(self, t0, t1):
         """continue a greedy loop that `decode_stop` cut at iteration t0 (gvl_amd.parallel.GraphedEvalForward captures
@@ -931,39 +836,8 @@ class Captioner(nn.Module):
         self._greedy_iterations(st, t0, t1)
         return st["alive"][t0 - 1:t1 - 1].view(torch.bool)
 
-    def _decode_graphed(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi, beam=(1, 0.0)):
-        """Greedy decoding replayed from a hipGraph: the 31-step loop is ~800 kernel launches whose host-side issue
-        cost exceeds their run time; captured once per input shape, replayed with one launch.
-        beam = (beam_size, length_penalty) with beam_size > 1: the beam search (_beam_device) instead, by the same cache."""
-        cache = self.__dict__.get("_decode_graphs")
-        if cache is None:
-            cache = self._decode_graphs = _LRU(16)
-        # weight-derived operands are cached per parameter version (_inference_weights, _embedding_gates) and become
-        # constants of the captured graph: a parameter update must therefore lead to a new capture
-        key = (tuple(hs.shape), tuple(reference.shape), tuple(memory.shape), str(hs.device),
-               tuple(tshapes._gvl_host_lengths[0]),
-               torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else None, tuple(beam),
-               sum(p_._version for p_ in self.parameters()))
-        if cache and next(iter(cache))[-1] != key[-1]:
-            cache.clear()                                    # parameters changed: graphs of the old weights are dead
-        entry = cache.lookup(key)
-        if entry is None:
-            static = [t_.clone() for t_ in (hs, reference, memory, mask, valid_ratios)]
-            if beam[0] > 1:
-                decode = lambda: self._beam_device(*static, tshapes, lsi, *beam)      # noqa: E731
-            else:
-                decode = lambda: self._decode_device(*static, tshapes, lsi, 1, 1.0)   # noqa: E731
-            with side_stream(hs.device) as side:                # warm-up off the capture (lazy inits, LDS attributes)
-                decode()
-            with capture_on(side) as graph:
-                outs = decode()
-            entry = (graph, static, outs)
-            cache.store(key, entry)
-        graph, static, outs = entry
-        for dst, src in zip(static, (hs, reference, memory, mask, valid_ratios)):
-            dst.copy_(src)
-        graph.replay()
-        return outs
+    def _greedy_device(self, *args):
+        return self._decode_device(*args, 1, 1.0)                      # sample_max, temperature
 
     @_bf16_decode
     def sample(self, hs, reference, others, opt={}):
@@ -973,18 +847,12 @@ class Captioner(nn.Module):
         temperature = opt.get('temperature', 1.0)
         beam_size = int(opt.get('beam_size', 1) or 1)
         if beam_size > 1:
-            # the best beam in the greedy branch's form: (n, keep) with keep = the longest returned caption, ([], []) when
-            # every one is empty -- PostProcess reads it as it reads greedy output
             if not sample_max:
                 raise ValueError("beam_size > 1 needs sample_max = 1: beam search and multinomial sampling exclude each other")
             if getattr(self, "defer_trim", False):
                 raise NotImplementedError("beam search inside a captured whole forward (defer_trim) is not built")
-            res = self.beam_search(hs, reference, others, beam_size, opt.get('length_penalty', 0.0))
-            keep = int(res["lengths"][:, 0].max())                   # the one host read
-            if keep == 0:
-                return [], []
-            return res["tokens"][:, 0, :keep].clone(), res["logprobs"][:, 0, :keep].clone()
-        memory, tshapes, lsi, mask, _ = self._level_inputs(others, reference)
+            return self._best_beam(self.beam_search(hs, reference, others, beam_size, opt.get('length_penalty', 0.0)))
+        memory, tshapes, lsi, mask = self._level_inputs(others)
         if getattr(self, "defer_trim", False):
             # caller is capturing the whole forward in a hipGraph (gvl_amd.parallel.GraphedEvalForward): no host read
             # here; the untrimmed sequences are returned and the caller cuts them at `last_alive` after the replay
@@ -998,12 +866,7 @@ class Captioner(nn.Module):
         else:
             seq, seq_lp, alive = self._decode_device(hs, reference, memory, mask, others['valid_ratios'], tshapes,
                                                      lsi, sample_max, temperature)
-        # the reference stops at the first step where every row has finished (:186-187): one host read here
-        alive = alive.cpu().tolist()
-        keep = alive.index(False) if False in alive else len(alive)
-        if keep == 0:
-            return [], []
-        return seq[:, :keep].clone(), seq_lp[:, :keep].clone()
+        return self._trimmed(seq, seq_lp, alive)
 
 
 class LSTMDSACaptioner(Captioner):

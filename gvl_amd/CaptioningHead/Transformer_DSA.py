@@ -35,12 +35,11 @@ import torch.nn.functional as F
 
 from .. import MultiScaleDeformableAttention as MSDA
 from .. import _lib
-from ..graphs import _LRU, capture_on, side_stream
 from ..linear import split_gemm_enabled
 from ..ops.functions import MSDeformAttnFunction
 from ..ops.modules import MSDeformAttn
 from ..ops.modules.ms_deform_attn import temporal_shapes_2d
-from .LSTM_DSA import _fp32_island
+from .decoding import BeamBooks, DecodingHead, _fp32_island, zero_views
 
 
 # ---- the two kernels of the token step -----------------------------------------------------------------------------------------
@@ -62,13 +61,22 @@ def embed_step(embed_weight, pos_table, it, t):
     return x, am
 
 
-def attend_kernel_eligible(qkv, x, cache, H):
-    """domain of gvl_capt_attend_f32: fp32 on the device, head dimension 64, H <= 8, at most 64 cached positions"""
+def attend_beam_kernel_eligible(qkv, x, cache, lineage, H):
+    """domain of gvl_capt_attend_f32 (lineage None): fp32 on the device, head dimension 64, H <= 8, at most 64 cached positions; of
+    gvl_capt_attend_beam_f32: that, a contiguous uint8 lineage table and at most 8 beams"""
     C = x.shape[1]
-    return bool(x.is_cuda and qkv.dtype == x.dtype == cache.dtype == torch.float32 and C % H == 0 and qkv.stride(1) == 1
-                and x.stride(1) == 1 and qkv.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and cache.is_contiguous()
-                and qkv.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
-                and _lib.lib().gvl_capt_attend_applicable(H, C // H, cache.shape[2]))
+    if not (x.is_cuda and qkv.dtype == x.dtype == cache.dtype == torch.float32 and C % H == 0 and qkv.stride(1) == 1
+            and x.stride(1) == 1 and qkv.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and cache.is_contiguous()
+            and qkv.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0):
+        return False
+    if lineage is None:
+        return bool(_lib.lib().gvl_capt_attend_applicable(H, C // H, cache.shape[2]))
+    return bool(lineage.is_contiguous() and _lib.lib().gvl_capt_attend_beam_applicable(H, C // H, cache.shape[2], lineage.shape[1]))
+
+
+def attend_kernel_eligible(qkv, x, cache, H):
+    """domain of gvl_capt_attend_f32"""
+    return attend_beam_kernel_eligible(qkv, x, cache, None, H)
 
 
 def attend_step_torch(qkv, x, cache, t, H, weight, bias, eps):
@@ -91,32 +99,7 @@ def attend_step(qkv, x, cache, t, H, weight, bias, eps, want_amax=False):
     (nothing else of it), attends over positions 0..t per head at scale 1 / sqrt(D), adds the residual and applies the LayerNorm
     (weight, bias, eps) -> (y (n, C), max |y[r]| (n,) or None).  gvl_capt_attend_f32 where it applies (attend_kernel_eligible),
     the PyTorch formulation of the same step otherwise."""
-    n, C = x.shape
-    assert qkv.shape == (n, 3 * C) and cache.shape[:2] == (2, n) and cache.shape[3] == C and 0 <= t < cache.shape[2]
-    if attend_kernel_eligible(qkv, x, cache, H):
-        y = torch.empty(n, C, device=x.device, dtype=torch.float32)
-        am = torch.empty(n, device=x.device, dtype=torch.float32) if want_amax else None
-        with torch.cuda.device(x.device):
-            rc = _lib.lib().gvl_capt_attend_f32(qkv.data_ptr(), qkv.stride(0), x.data_ptr(), x.stride(0), cache.data_ptr(), n,
-                                                cache.shape[2], int(t), H, weight.data_ptr(), bias.data_ptr(), float(eps),
-                                                y.data_ptr(), am.data_ptr() if am is not None else None,
-                                                torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "capt_attend")
-        return y, am
-    y = attend_step_torch(qkv, x, cache, t, H, weight, bias, eps)
-    if want_amax:
-        from .. import layers as L
-        return y, L.row_absmax(y)[0]
-    return y, None
-
-
-def attend_beam_kernel_eligible(qkv, x, cache, lineage, H):
-    """domain of gvl_capt_attend_beam_f32: that of gvl_capt_attend_f32, a contiguous uint8 lineage table and at most 8 beams"""
-    C = x.shape[1]
-    return bool(x.is_cuda and qkv.dtype == x.dtype == cache.dtype == torch.float32 and C % H == 0 and qkv.stride(1) == 1
-                and x.stride(1) == 1 and qkv.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and cache.is_contiguous()
-                and qkv.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and lineage.is_contiguous()
-                and _lib.lib().gvl_capt_attend_beam_applicable(H, C // H, cache.shape[2], lineage.shape[1]))
+    return attend_step_beam(qkv, x, cache, None, t, H, weight, bias, eps, want_amax=want_amax)
 
 
 def attend_step_beam_torch(qkv, x, cache, lineage, t, H, weight, bias, eps):
@@ -141,21 +124,32 @@ def attend_step_beam(qkv, x, cache, lineage, t, H, weight, bias, eps, want_amax=
     (n, W, positions) uint8.  Row (r, j) writes k, v at position t of its own slot r W + j (nothing else of the cache is written) and
     attends over position p < t of slot r W + lineage[r, j, p] and over its own position t -- the cache is never re-ordered by
     parent beam, the table is (MSDA.beam_step_lineage).  Nothing at or behind t is read, of the cache or of the table; a byte above
-    W - 1 is read as W - 1.  gvl_capt_attend_beam_f32 where it applies, the PyTorch formulation of the same step otherwise."""
+    W - 1 is read as W - 1.  gvl_capt_attend_beam_f32 where it applies, the PyTorch formulation of the same step otherwise.
+    lineage None: the plain step (attend_step) -- one body for both."""
     R, C = x.shape
-    n, W, P = lineage.shape
-    assert R == n * W and qkv.shape == (R, 3 * C) and cache.shape == (2, R, P, C) and 0 <= t < P and lineage.dtype == torch.uint8
+    P = cache.shape[2]
+    assert qkv.shape == (R, 3 * C) and cache.shape == (2, R, P, C) and 0 <= t < P
+    if lineage is not None:
+        n, W, _ = lineage.shape
+        assert R == n * W and lineage.shape[2] == P and lineage.dtype == torch.uint8
     if attend_beam_kernel_eligible(qkv, x, cache, lineage, H):
         y = torch.empty(R, C, device=x.device, dtype=torch.float32)
         am = torch.empty(R, device=x.device, dtype=torch.float32) if want_amax else None
+        tail = (int(t), H, weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(), am.data_ptr() if am is not None else None)
         with torch.cuda.device(x.device):
-            rc = _lib.lib().gvl_capt_attend_beam_f32(qkv.data_ptr(), qkv.stride(0), x.data_ptr(), x.stride(0), cache.data_ptr(),
-                                                     lineage.data_ptr(), n, W, P, int(t), H, weight.data_ptr(), bias.data_ptr(),
-                                                     float(eps), y.data_ptr(), am.data_ptr() if am is not None else None,
-                                                     torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "capt_attend_beam")
+            stream = torch.cuda.current_stream().cuda_stream
+            if lineage is None:
+                rc = _lib.lib().gvl_capt_attend_f32(qkv.data_ptr(), qkv.stride(0), x.data_ptr(), x.stride(0), cache.data_ptr(), R,
+                                                    P, *tail, stream)
+            else:
+                rc = _lib.lib().gvl_capt_attend_beam_f32(qkv.data_ptr(), qkv.stride(0), x.data_ptr(), x.stride(0), cache.data_ptr(),
+                                                         lineage.data_ptr(), n, W, P, *tail, stream)
+        _lib.check(rc, "capt_attend" if lineage is None else "capt_attend_beam")
         return y, am
-    y = attend_step_beam_torch(qkv, x, cache, lineage, t, H, weight, bias, eps)
+    if lineage is None:
+        y = attend_step_torch(qkv, x, cache, t, H, weight, bias, eps)
+    else:
+        y = attend_step_beam_torch(qkv, x, cache, lineage, t, H, weight, bias, eps)
     if want_amax:
         from .. import layers as L
         return y, L.row_absmax(y)[0]
@@ -226,7 +220,9 @@ class TransformerDSACapLayer(nn.Module):
         return self.forward_ffn(x)
 
 
-class TransformerDSACaptioner(nn.Module):
+class TransformerDSACaptioner(DecodingHead):
+    _reference_line = "Transformer_DSA.py:196, as LSTM_DSA.py:151"
+
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
@@ -267,27 +263,12 @@ class TransformerDSACaptioner(nn.Module):
         table[:, 1::2] = torch.cos(pos * div_term)
         return table.unsqueeze(0)
 
+    def _vocab_layer(self):
+        return self.logits
+
     def build_loss(self, input, target, mask):
-        """Transformer_DSA.py:165-170: the last position predicts nothing and is dropped.  The reference multiplies by a
-        materialised one-hot tensor and sums the vocabulary axis, i.e. exactly the gathered log-prob -- taken directly here."""
-        input = input[:, :-1, :]
-        max_len = input.shape[1]
-        picked = input.gather(2, target[:, :max_len, None]).squeeze(2)
-        return -(picked * mask[:, :max_len]).sum(1) / (mask.sum(1) + 1e-6)
-
-    def _scaled_reference(self, reference, others):
-        vr = others['valid_ratios']
-        if reference.shape[-1] == 2:
-            return reference[:, :, None] * torch.stack([vr] * 2, -1)[:, None]
-        return reference[:, :, None] * vr[:, None, :, None]
-
-    def _level_inputs(self, others):
-        if self.n_levels < self.opt.num_feature_levels:
-            # (the reference's branch cannot run on temporal features: Transformer_DSA.py:196 takes torch.prod(dim=1) of the 1-D
-            #  tensor of level lengths, as LSTM_DSA.py:151 does; there is no behaviour to mirror)
-            raise NotImplementedError("cap_num_feature_levels < num_feature_levels: the reference itself raises on this branch for "
-                                      "temporal features (Transformer_DSA.py:196) and no config uses it")
-        return others['memory'], others['spatial_shapes'], others['level_start_index'], others['mask_flatten']
+        """Transformer_DSA.py:165-170: the last position predicts nothing and is dropped"""
+        return self._masked_row_nll(input[:, :-1, :], target, mask)
 
     @_fp32_island
     def forward(self, hs, reference, others, seq, steps=None):
@@ -323,19 +304,6 @@ class TransformerDSACaptioner(nn.Module):
                 and hs.is_contiguous() and C % 64 == 0 and C <= 1024 and memory.shape[-1] == C and len(self.layers) > 0):
             return False
         return all(L._attn_ok(l_.cross_attention, host, memory.shape[1]) and l_.linear1.out_features % 64 == 0 for l_ in self.layers)
-
-    def _logit_planes(self, x):
-        """fp16 planes of the vocabulary layer's weight, rebuilt when it changes; None when the split product does not apply"""
-        w = self.logits.weight
-        if (self.training or torch.is_grad_enabled() or torch.is_autocast_enabled() or x.dtype != torch.float32
-                or not split_gemm_enabled() or not MSDA.split_eligible(w)):
-            return None
-        key = (w.data_ptr(), w._version)
-        cached = self.__dict__.get("_logit_p")
-        if cached is None or cached[0] != key:
-            with torch.no_grad():
-                cached = self.__dict__["_logit_p"] = (key, MSDA.split_rows(w.detach()))
-        return cached[1]
 
     def _torch_weights(self):
         """[query; key; value] of every layer as one matrix, for the PyTorch form of the token step: per parameter version"""
@@ -387,8 +355,6 @@ class TransformerDSACaptioner(nn.Module):
     def _attend(self, i, layer, qkv, x, t, st, want_amax=False):
         """the cached self-attention of a token step: through the beams' lineage table when the state carries one (_beam_device)"""
         norm = layer.norm1
-        if st.get("lineage") is None:
-            return attend_step(qkv, x, st["cache"][i], t, self.n_heads, norm.weight, norm.bias, norm.eps, want_amax=want_amax)
         return attend_step_beam(qkv, x, st["cache"][i], st["lineage"], t, self.n_heads, norm.weight, norm.bias, norm.eps,
                                 want_amax=want_amax)
 
@@ -444,55 +410,68 @@ class TransformerDSACaptioner(nn.Module):
         x2 = layer.norm2(z + F.linear(o, att.output_proj.weight, att.output_proj.bias))
         return layer.norm3(x2 + layer.linear2(F.relu(layer.linear1(x2))))
 
+    def _token_state(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi, W, positions):
+        """what the token steps of one decode read and write beside their ids, for W rows per event (W > 1: the beams of an
+        event, W consecutive rows -- the event's reference points and its half of dim_project repeated over them):
+        value_proj(memory) per video and layer, the key / value cache of `positions` positions per row, the arena of row maxima or
+        the concatenated q | k | v weights.  st["lineage"] stays None in the greedy loop; the beam search sets its table per token."""
+        from .. import layers as L
+        B, Q, C = hs.shape
+        n, T, nl, dev = B * Q, self.max_caption_len, len(self.layers), hs.device
+        hs = hs.contiguous()
+        fast = self._layers_ok(hs, memory, tshapes)
+        values, qparts = self._decode_constants(hs.view(n, C), memory, mask, fast)
+        if W > 1:
+            qparts = [q_.repeat_interleave(W, 0) for q_ in qparts]
+            reference = reference.repeat_interleave(W, 1)
+        st = {"B": B, "Q": Q * W, "values": values, "qparts": qparts, "tshapes": tshapes, "lsi": lsi, "fast": fast, "lineage": None,
+              "ref_in": self._scaled_reference(reference, {'valid_ratios': valid_ratios}).contiguous(),
+              "shapes2d": temporal_shapes_2d(tshapes, lsi), "host": getattr(tshapes, "_gvl_host_lengths", None),
+              # keys and values of every layer; position p of a row is written by step p and read by the steps behind it only (beam
+              # search: by the beam that sits at the row then, and read through the lineages)
+              "cache": torch.empty(nl, 2, n * W, positions, C, device=dev, dtype=torch.float32),
+              "pos_table": self.pos_table[0], "kernel_embed": C % 4 == 0 and self.embed.weight.dtype == torch.float32}
+        if fast:
+            st["arena"] = L._Arena((3 * T * nl + 2) * (n * W + 4), dev)
+        else:
+            st["qkv_w"] = self._torch_weights()
+        return st
+
+    def _token_step(self, it, t, st):
+        """ids (rows,) of position t -> the rows of the last layer (rows, C): the embedding + position row, then every layer on the
+        hand-written launches or on PyTorch's (st["fast"])"""
+        fast, pos_table = st["fast"], st["pos_table"]
+        if st["kernel_embed"]:
+            x, am = embed_step(self.embed.weight, pos_table, it, t)
+        else:
+            x, am = self.embed.weight[it] + (pos_table[t] if t < pos_table.shape[0] else 0.0), None
+            if fast:
+                from .. import layers as L
+                am, _ = L.row_absmax(x)
+        for i, layer in enumerate(self.layers):
+            if fast:
+                x, am = self._layer_step_fast(i, layer, x, am, t, st)
+            else:
+                x = self._layer_step_torch(i, layer, x, t, st)
+        return x
+
     def _decode_device(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi):
         """The whole greedy loop on the device, no host interaction: -> (seq (n, T), logprob (n, T), alive (T,)), T = max_caption_len.
         Capturable in a hipGraph.  Iteration t first books token t - 1 from the logits of the previous iteration (argmax, log-prob,
         unfinished / alive flags: one launch), then runs position t through the layers.  The reference also runs the layers after the
         LAST token (:237) and then leaves the loop without reading the result."""
-        from .. import layers as L
-        B, Q, C = hs.shape
-        n, T, nl, dev = B * Q, self.max_caption_len, len(self.layers), hs.device
-        hs = hs.contiguous()
-        hs2 = hs.view(n, C)
-        fast = self._layers_ok(hs, memory, tshapes)
-        values, qparts = self._decode_constants(hs2, memory, mask, fast)
-        st = {"B": B, "Q": Q, "values": values, "qparts": qparts, "tshapes": tshapes, "lsi": lsi,
-              "ref_in": self._scaled_reference(reference, {'valid_ratios': valid_ratios}).contiguous(),
-              "shapes2d": temporal_shapes_2d(tshapes, lsi), "host": getattr(tshapes, "_gvl_host_lengths", None),
-              # keys and values of every layer; position p is written by step p and read by the steps behind it only
-              "cache": torch.empty(nl, 2, n, T + 1, C, device=dev, dtype=torch.float32)}
-        if fast:
-            st["arena"] = L._Arena((3 * T * nl + 2) * (n + 4), dev)
-        else:
-            st["qkv_w"] = self._torch_weights()
-        # ONE zero fill, as LSTM_DSA.Captioner._decode_device: the log-prob table, the <bos> ids + the token table, the `alive` flags
-        b_f = (4 * n * T + 15) // 16 * 16
-        b_l = (8 * (n + n * T) + 15) // 16 * 16
-        raw = torch.zeros(b_f + b_l + T, dtype=torch.uint8, device=dev)
-        seq_lp = raw[:4 * n * T].view(torch.float32).view(n, T)
-        longs = raw[b_f:b_f + 8 * (n + n * T)].view(torch.long)
-        it, seq = longs[:n], longs[n:].view(n, T)
-        alive = raw[b_f + b_l:]
+        n, T, dev = hs.shape[0] * hs.shape[1], self.max_caption_len, hs.device
+        st = self._token_state(hs, reference, memory, mask, valid_ratios, tshapes, lsi, 1, T + 1)
+        # ONE zero fill, as LSTM_DSA.Captioner._decode_device: the log-prob table, the <bos> ids, the token table, the `alive` flags
+        seq_lp, it, seq, alive = zero_views(dev, (torch.float32, (n, T)), (torch.long, (n,)), (torch.long, (n, T)), (torch.uint8, (T,)))
         unfinished = torch.empty(n, dtype=torch.uint8, device=dev)
-        pos_table = self.pos_table[0]
-        kernel_embed = C % 4 == 0 and self.embed.weight.dtype == torch.float32
         logits = None
         for t in range(T + 1):
             if t > 0:
                 it = MSDA.greedy_step(logits, t - 1, unfinished, seq, seq_lp, alive)      # (the raw argmax is the next input, :230-232)
             if t == T:
                 break
-            if kernel_embed:
-                x, am = embed_step(self.embed.weight, pos_table, it, t)
-            else:
-                x, am = self.embed.weight[it] + (pos_table[t] if t < pos_table.shape[0] else 0.0), None
-            if fast and am is None:
-                am, _ = L.row_absmax(x)
-            for i, layer in enumerate(self.layers):
-                if fast:
-                    x, am = self._layer_step_fast(i, layer, x, am, t, st)
-                else:
-                    x = self._layer_step_torch(i, layer, x, t, st)
+            x = self._token_step(it, t, st)
             planes = self._logit_planes(x)
             if planes is not None:                                   # fp32 product on the fp16 matrix cores, argmax in its epilogue
                 logits = MSDA.gemm_f16x3_argmax(MSDA.split_rows(x), planes, self.logits.bias)      # never written out
@@ -508,127 +487,24 @@ class TransformerDSACaptioner(nn.Module):
         the cache is NOT re-ordered for that.  Every row appends at its own slot; the kernel that selects the beams
         (gvl_beam_step_lineage_f32, one launch per token) re-orders a byte table that names, per beam and position, the slot holding
         it, and the attention (attend_step_beam) reads through that table -- one table for all layers."""
-        from .. import layers as L
-        W, T, V1 = beam_size, self.max_caption_len, self.vocab_size + 1
-        B, Q, C = hs.shape
-        n, nl, dev = B * Q, len(self.layers), hs.device
-        R = n * W
-        hs = hs.contiguous()
-        fast = self._layers_ok(hs, memory, tshapes)
-        # value_proj(memory) per video, the event-feature half of dim_project per EVENT and repeated over its beams
-        values, qparts = self._decode_constants(hs.view(n, C), memory, mask, fast)
-        qparts = [q_.repeat_interleave(W, 0) for q_ in qparts]
+        W, T = beam_size, self.max_caption_len
+        n, dev = hs.shape[0] * hs.shape[1], hs.device
+        st = self._token_state(hs, reference, memory, mask, valid_ratios, tshapes, lsi, W, T)
         # ONE zero fill: the <bos> ids, the `alive` words, the first step's finished flags, the two lineage tables
-        b_l = (8 * R + 15) // 16 * 16
-        raw = torch.zeros(b_l + 4 * T + R + 2 * R * T, dtype=torch.uint8, device=dev)
-        it = raw[:8 * R].view(torch.long)
-        alive = raw[b_l:b_l + 4 * T].view(torch.int32)
-        fin = raw[b_l + 4 * T:b_l + 4 * T + R].view(n, W)
-        lins = raw[b_l + 4 * T + R:].view(2, n, W, T)
-        st = {"B": B, "Q": Q * W, "values": values, "qparts": qparts, "tshapes": tshapes, "lsi": lsi,
-              "ref_in": self._scaled_reference(reference.repeat_interleave(W, 1), {'valid_ratios': valid_ratios}).contiguous(),
-              "shapes2d": temporal_shapes_2d(tshapes, lsi), "host": getattr(tshapes, "_gvl_host_lengths", None),
-              # position p of slot s is written by step p, by the beam that sits at s then, and read through the lineages behind it
-              "cache": torch.empty(nl, 2, R, T, C, device=dev, dtype=torch.float32)}
-        if fast:
-            st["arena"] = L._Arena((3 * T * nl + 2) * (R + 4), dev)
-        else:
-            st["qkv_w"] = self._torch_weights()
-        score = torch.full((n, W), float("-inf"), dtype=torch.float32, device=dev)
-        score[:, 0] = 0.0                                              # beam 0 alone is live: the first step yields W distinct beams
-        scores = (torch.empty_like(score), torch.empty_like(score))
-        fins = (torch.empty_like(fin), torch.empty_like(fin))
-        parents = torch.empty(T, n, W, dtype=torch.int32, device=dev)
-        tokens = torch.empty(T, n, W, dtype=torch.long, device=dev)
-        logps = torch.empty(T, n, W, dtype=torch.float32, device=dev)
-        ld = (V1 + 3) // 4 * 4                                          # rows of the logits padded to 16 bytes
-        logit_buf = torch.empty(R, ld, dtype=torch.float32, device=dev)
-        pos_table = self.pos_table[0]
-        kernel_embed = C % 4 == 0 and self.embed.weight.dtype == torch.float32
-        for t in range(T):
+        it, alive, fin, lins = zero_views(dev, (torch.long, (n * W,)), (torch.int32, (T,)), (torch.uint8, (n, W)),
+                                          (torch.uint8, (2, n, W, T)))
+        books = BeamBooks(n, W, T, self.vocab_size + 1, fin, alive, dev)
+        for t, (ins, outs, it_next) in enumerate(books.steps):
             st["lineage"] = lins[t & 1]                                 # positions [0, t) of the current beams
-            if kernel_embed:
-                x, am = embed_step(self.embed.weight, pos_table, it, t)
-            else:
-                x, am = self.embed.weight[it] + (pos_table[t] if t < pos_table.shape[0] else 0.0), None
-            if fast and am is None:
-                am, _ = L.row_absmax(x)
-            for i, layer in enumerate(self.layers):
-                if fast:
-                    x, am = self._layer_step_fast(i, layer, x, am, t, st)
-                else:
-                    x = self._layer_step_torch(i, layer, x, t, st)
+            x = self._token_step(it, t, st)
             planes = self._logit_planes(x)
             if planes is not None:                                      # fp32 product on the fp16 matrix cores, logits written
-                logits = MSDA.gemm_f16x3(MSDA.split_rows(x), planes, self.logits.bias, out=logit_buf[:, :V1])
+                logits = MSDA.gemm_f16x3(MSDA.split_rows(x), planes, self.logits.bias, out=books.logits_out)
             else:
                 logits = F.linear(x, self.logits.weight, self.logits.bias).float().contiguous()
-            MSDA.beam_step_lineage(logits, score, fin, lins[t & 1], lins[(t + 1) & 1], t, scores[t & 1], fins[t & 1], parents[t],
-                                   tokens[t], logps[t], alive[t:t + 1])
-            score, fin, it = scores[t & 1], fins[t & 1], tokens[t].view(-1)
-        return MSDA.beam_finish(parents, tokens, logps, score, length_penalty) + (alive != 0,)
-
-    def beam_search(self, hs, reference, others, beam_size, length_penalty=0.0):
-        """Beam-search decoding over the KV cache (semantics: DESIGN.md section 4.3, as LSTM_DSA.Captioner.beam_search) -> dict, every
-        entry in final rank order (rank = score / len ** length_penalty, len = emitted tokens with the end token; the penalty is never
-        applied during the search):
-            tokens (n, W, T) int64 and logprobs (n, W, T), zero behind a beam's end token;  scores (n, W) sum of log-probs;
-            lengths (n, W) tokens in front of the end token;  alive (T,) bool: some beam is still live after token t.
-        No host read in here.  With graph_decode set the loop is replayed from a hipGraph: the outputs are then the graph's static
-        tensors, overwritten by the next call."""
-        W = int(beam_size)
-        if not 1 <= W <= MSDA.BEAM_MAX:
-            raise ValueError(f"beam_size must be 1 .. {MSDA.BEAM_MAX} (got {beam_size})")
-        if W > self.vocab_size + 1:
-            raise ValueError(f"beam_size {W} exceeds the {self.vocab_size + 1} vocabulary entries")
-        if not hs.is_cuda:
-            raise NotImplementedError(f"beam_size > 1: the Transformer-DSA head searches on a ROCm device only (no CPU fallback); "
-                                      f"got {hs.device}")
-        if torch.is_autocast_enabled():
-            raise NotImplementedError("beam search decodes in fp32: the bf16-storage decode under torch.autocast is not built")
-        if torch.is_grad_enabled():
-            raise RuntimeError("beam search is inference only: call it under torch.no_grad()")
-        memory, tshapes, lsi, mask = self._level_inputs(others)
-        args = (hs, reference, memory, mask, others['valid_ratios'], tshapes, lsi)
-        if getattr(self, "graph_decode", False) and getattr(tshapes, "_gvl_host_lengths", None) is not None:
-            out = self._decode_graphed(*args, beam=(W, float(length_penalty)))
-        else:
-            out = self._beam_device(*args, W, float(length_penalty))
-        return dict(zip(("tokens", "logprobs", "scores", "lengths", "alive"), out))
-
-    def _decode_graphed(self, hs, reference, memory, mask, valid_ratios, tshapes, lsi, beam=(1, 0.0)):
-        """the greedy loop replayed from a hipGraph, captured once per input shape and parameter version (as
-        LSTM_DSA.Captioner._decode_graphed).  beam = (beam_size, length_penalty) with beam_size > 1: the beam search (_beam_device)
-        instead, by the same cache."""
-        cache = self.__dict__.get("_decode_graphs")
-        if cache is None:
-            cache = self.__dict__["_decode_graphs"] = _LRU(16)
-        # weight-derived operands (planes, concatenated matrices) are cached per parameter version and become constants of the
-        # captured graph: a parameter update must lead to a new capture
-        key = (tuple(hs.shape), tuple(reference.shape), tuple(memory.shape), str(hs.device), tuple(tshapes._gvl_host_lengths[0]),
-               mask is not None, tuple(beam), sum(p_._version for p_ in self.parameters()))
-        if cache and next(iter(cache))[-1] != key[-1]:
-            cache.clear()                                    # parameters changed: graphs of the old weights are dead
-        entry = cache.lookup(key)
-        ins = [t_ for t_ in (hs, reference, memory, mask, valid_ratios)]
-        if entry is None:
-            static = [t_.clone() if t_ is not None else None for t_ in ins]
-            if beam[0] > 1:
-                decode = lambda: self._beam_device(*static, tshapes, lsi, *beam)      # noqa: E731
-            else:
-                decode = lambda: self._decode_device(*static, tshapes, lsi)      # noqa: E731
-            with side_stream(hs.device) as side:                # warm-up off the capture (lazy inits, weight planes)
-                decode()
-            with capture_on(side) as graph:
-                outs = decode()
-            entry = (graph, static, outs)
-            cache.store(key, entry)
-        graph, static, outs = entry
-        for dst, src in zip(static, ins):
-            if dst is not None:
-                dst.copy_(src)
-        graph.replay()
-        return outs
+            MSDA.beam_step_lineage(logits, *ins, lins[t & 1], lins[(t + 1) & 1], t, *outs)
+            it = it_next
+        return books.finish(length_penalty)
 
     @_fp32_island
     def sample(self, hs, reference, others, opt={}):
@@ -642,16 +518,10 @@ class TransformerDSACaptioner(nn.Module):
             raise NotImplementedError('Do not support scale logprobs by temperture')            # (the reference's own, :235)
         beam_size = int(opt.get('beam_size', 1) or 1)
         if beam_size > 1:
-            # the best beam in the greedy branch's form: (n, keep) with keep = the longest returned caption, ([], []) when
-            # every one is empty -- PostProcess reads it as it reads greedy output
             if getattr(self, "defer_trim", False):
                 raise NotImplementedError("beam search inside a captured whole forward (defer_trim) is not built")
             with torch.no_grad():
-                res = self.beam_search(hs, reference, others, beam_size, opt.get('length_penalty', 0.0))
-            keep = int(res["lengths"][:, 0].max())                   # the one host read
-            if keep == 0:
-                return [], []
-            return res["tokens"][:, 0, :keep].clone(), res["logprobs"][:, 0, :keep].clone()
+                return self._best_beam(self.beam_search(hs, reference, others, beam_size, opt.get('length_penalty', 0.0)))
         memory, tshapes, lsi, mask = self._level_inputs(others)
         if not hs.is_cuda:
             raise RuntimeError(f"gvl_amd's Transformer-DSA head decodes on a ROCm device only (no CPU fallback); got {hs.device}")
@@ -665,9 +535,4 @@ class TransformerDSACaptioner(nn.Module):
                 seq, seq_lp, alive = self._decode_graphed(*args)
             else:
                 seq, seq_lp, alive = self._decode_device(*args)
-        # the reference stops at the first step where every row has finished (:246-247): one host read here
-        alive = alive.cpu().tolist()
-        keep = alive.index(False) if False in alive else len(alive)
-        if keep == 0:
-            return [], []
-        return seq[:, :keep].clone(), seq_lp[:, :keep].clone()
+        return self._trimmed(seq, seq_lp, alive)

@@ -853,31 +853,39 @@ def greedy_step_and_gemm(logits, t_col, unfinished, seq, seq_lp, alive, a, b, bi
 BEAM_MAX = 8          # include/gvl_msda.h: gvl_beam_step_f32 serves 1 <= W <= 8
 
 
+def _beam_step_checks(fn, logits, score_in, fin_in, score_out, fin_out, parent, token, logp, alive, reordered):
+    """the argument checks the two beam steps share, in one order: the scores' shape, the beam width, the logits, then the caller's
+    own -- reordered(n, W) checks what only it knows and returns rows (name, in, out, dtype, shape) of the buffers it re-orders by
+    parent -- then shape / dtype / contiguity of every buffer, and that every in / out pair ping-pongs -> (n, W, V)"""
+    _require(score_in.dim() == 2, f"{fn}: score_in must be (n, W)")
+    n, W = score_in.shape
+    _require(1 <= W <= BEAM_MAX, f"{fn}: beam width must be 1 .. {BEAM_MAX} (got {W})")
+    _require(logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == n * W
+             and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1] and logits.shape[1] >= W,
+             f"{fn}: logits must be an (n W, V >= W) fp32 CUDA matrix with unit column stride")
+    pairs = (("score", score_in, score_out, torch.float32, (n, W)), ("fin", fin_in, fin_out, torch.uint8, (n, W))) + reordered(n, W)
+    table = [(name + end, t_, dt, shape) for name, a, b, dt, shape in pairs for end, t_ in (("_in", a), ("_out", b))]
+    table += [("parent", parent, torch.int32, (n, W)), ("token", token, torch.int64, (n, W)), ("logp", logp, torch.float32, (n, W)),
+              ("alive", alive, torch.int32, (1,))]
+    for name, t_, dt, shape in table:
+        _require(t_.device == logits.device and t_.dtype == dt and tuple(t_.shape) == shape and t_.is_contiguous(),
+                 f"{fn}: {name} must be a contiguous {dt} tensor of shape {shape} on the logits' device")
+    for name, a, b, _, _ in pairs:
+        _require(a.data_ptr() != b.data_ptr(), f"{fn}: {name}_in and {name}_out ping-pong, nothing is updated in place")
+    return n, W, logits.shape[1]
+
+
 def beam_step(logits, score_in, fin_in, h_in, c_in, score_out, fin_out, parent, token, logp, alive, h_out, c_out):
     """one token of the beam search (include/gvl_msda.h: gvl_beam_step_f32): logits (n W, V) fp32 with unit column stride (the
     row stride may be padded), score_in / fin_in (n, W) fp32 / uint8, h_in / c_in (n W, H) the state rows the step left.  Writes
     the W best continuations of every event row in descending order of score -- score_out, fin_out, parent (int32), token
     (int64: also the next step's input ids), logp, all (n, W) -- the rows of h_in / c_in re-ordered by parent into h_out / c_out,
     and ORs 1 into alive (one int32, zero-initialised) when a beam is still live after the step."""
-    _require(score_in.dim() == 2, "beam_step: score_in must be (n, W)")
-    n, W = score_in.shape
-    _require(1 <= W <= BEAM_MAX, f"beam_step: beam width must be 1 .. {BEAM_MAX} (got {W})")
-    _require(logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == n * W
-             and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1] and logits.shape[1] >= W,
-             "beam_step: logits must be an (n W, V >= W) fp32 CUDA matrix with unit column stride")
-    V = logits.shape[1]
-    _require(h_in.dim() == 2 and h_in.shape[0] == n * W and h_in.shape[1] % 4 == 0, "beam_step: h_in must be (n W, H), H % 4 == 0")
+    def states(n, W):
+        _require(h_in.dim() == 2 and h_in.shape[0] == n * W and h_in.shape[1] % 4 == 0, "beam_step: h_in must be (n W, H), H % 4 == 0")
+        return (("h", h_in, h_out, torch.float32, tuple(h_in.shape)), ("c", c_in, c_out, torch.float32, tuple(h_in.shape)))
+    n, W, V = _beam_step_checks("beam_step", logits, score_in, fin_in, score_out, fin_out, parent, token, logp, alive, states)
     H = h_in.shape[1]
-    for name, t_, dt, shape in (("score_in", score_in, torch.float32, (n, W)), ("fin_in", fin_in, torch.uint8, (n, W)),
-                                ("score_out", score_out, torch.float32, (n, W)), ("fin_out", fin_out, torch.uint8, (n, W)),
-                                ("parent", parent, torch.int32, (n, W)), ("token", token, torch.int64, (n, W)),
-                                ("logp", logp, torch.float32, (n, W)), ("alive", alive, torch.int32, (1,)),
-                                ("h_in", h_in, torch.float32, (n * W, H)), ("c_in", c_in, torch.float32, (n * W, H)),
-                                ("h_out", h_out, torch.float32, (n * W, H)), ("c_out", c_out, torch.float32, (n * W, H))):
-        _require(t_.device == logits.device and t_.dtype == dt and tuple(t_.shape) == shape and t_.is_contiguous(),
-                 f"beam_step: {name} must be a contiguous {dt} tensor of shape {shape} on the logits' device")
-    for name, a, b in (("h", h_in, h_out), ("c", c_in, c_out), ("score", score_in, score_out), ("fin", fin_in, fin_out)):
-        _require(a.data_ptr() != b.data_ptr(), f"beam_step: {name}_in and {name}_out ping-pong, nothing is updated in place")
     _require(all(t_.data_ptr() % 16 == 0 for t_ in (h_in, c_in, h_out, c_out)), "beam_step: the state buffers must be 16-byte aligned")
     with torch.cuda.device(logits.device):
         rc = _lib.lib().gvl_beam_step_f32(logits.data_ptr(), logits.stride(0), n, W, V, score_in.data_ptr(), fin_in.data_ptr(),
@@ -895,26 +903,14 @@ def beam_step_lineage(logits, score_in, fin_in, lin_in, lin_out, t, score_out, f
     the same records; in place of the state rows it re-orders lin_in (n, W, P) uint8 -- per beam and cache position the slot of
     the event that holds it -- into lin_out: the parent's bytes in front of position t, the parent itself at t (the position the
     step just computed), nothing behind t.  At t = 0 nothing of lin_in is read.  The tables may start at any byte."""
-    _require(score_in.dim() == 2, "beam_step_lineage: score_in must be (n, W)")
-    n, W = score_in.shape
-    _require(1 <= W <= BEAM_MAX, f"beam_step_lineage: beam width must be 1 .. {BEAM_MAX} (got {W})")
-    _require(logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == n * W
-             and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1] and logits.shape[1] >= W,
-             "beam_step_lineage: logits must be an (n W, V >= W) fp32 CUDA matrix with unit column stride")
-    V = logits.shape[1]
-    _require(lin_in.dim() == 3 and 1 <= lin_in.shape[2] <= LINEAGE_MAX,
-             f"beam_step_lineage: lin_in must be (n, W, P) with 1 <= P <= {LINEAGE_MAX} cache positions")
+    def tables(n, W):
+        _require(lin_in.dim() == 3 and 1 <= lin_in.shape[2] <= LINEAGE_MAX,
+                 f"beam_step_lineage: lin_in must be (n, W, P) with 1 <= P <= {LINEAGE_MAX} cache positions")
+        P = lin_in.shape[2]
+        _require(0 <= int(t) < P, f"beam_step_lineage: the position must be 0 <= t < P = {P} (got {t})")
+        return (("lin", lin_in, lin_out, torch.uint8, (n, W, P)),)
+    n, W, V = _beam_step_checks("beam_step_lineage", logits, score_in, fin_in, score_out, fin_out, parent, token, logp, alive, tables)
     P = lin_in.shape[2]
-    _require(0 <= int(t) < P, f"beam_step_lineage: the position must be 0 <= t < P = {P} (got {t})")
-    for name, t_, dt, shape in (("score_in", score_in, torch.float32, (n, W)), ("fin_in", fin_in, torch.uint8, (n, W)),
-                                ("score_out", score_out, torch.float32, (n, W)), ("fin_out", fin_out, torch.uint8, (n, W)),
-                                ("parent", parent, torch.int32, (n, W)), ("token", token, torch.int64, (n, W)),
-                                ("logp", logp, torch.float32, (n, W)), ("alive", alive, torch.int32, (1,)),
-                                ("lin_in", lin_in, torch.uint8, (n, W, P)), ("lin_out", lin_out, torch.uint8, (n, W, P))):
-        _require(t_.device == logits.device and t_.dtype == dt and tuple(t_.shape) == shape and t_.is_contiguous(),
-                 f"beam_step_lineage: {name} must be a contiguous {dt} tensor of shape {shape} on the logits' device")
-    for name, a, b in (("lin", lin_in, lin_out), ("score", score_in, score_out), ("fin", fin_in, fin_out)):
-        _require(a.data_ptr() != b.data_ptr(), f"beam_step_lineage: {name}_in and {name}_out ping-pong, nothing is updated in place")
     with torch.cuda.device(logits.device):
         rc = _lib.lib().gvl_beam_step_lineage_f32(logits.data_ptr(), logits.stride(0), n, W, V, score_in.data_ptr(),
                                                   fin_in.data_ptr(), lin_in.data_ptr(), P, int(t), score_out.data_ptr(),

@@ -404,7 +404,7 @@ def test_path_census_at_the_real_dimensions(monkeypatch):
               "level_start_index": ls, "valid_ratios": torch.ones(B, 4, device=DEV)}
 
     def greedy():
-        memory, tshapes, lsi, mask, _ = cap._level_inputs(others, reference)
+        memory, tshapes, lsi, mask = cap._level_inputs(others)
         real = cap.core.prepare
 
         def prepare(*a):                                             # (h_planes_only off: the fp32 h is written, as in the search)
